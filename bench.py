@@ -25,6 +25,14 @@ CPU baseline: the oracle (oracle/rips_oracle.c, a C restatement of the
 ripser semantics; "kind": "port") on the same inputs, 1 core and P worker
 processes (the host CPUs this job may use: 16 per GPU, the whole host at
 8 GPUs), on bounded samples.  Prints ONE JSON line on rank 0.
+
+A plain run (``--gpus 1 --steps K --warmup W``) sets up, warms up, times the K
+steps of the primary workload and prints the line (``value``, ``ms_per_step``);
+``--dump-outputs DIR`` also writes the last step's diagrams (dump_outputs).
+Everything else above -- ``workloads``, the CPU baselines, the
+one-call-at-a-time pass, the stage pass behind ``roofline`` and ``stages_ms``,
+the strong-scaling record of a weak multi-GPU run -- takes runs of its own and
+is measured only with ``--full``.
 """
 from __future__ import annotations
 
@@ -290,16 +298,19 @@ def cpu_baseline(pool, P: int, name: str, X, maxdim: int, seconds: float) -> dic
 
 
 # ---------------------------------------------------------------- GPU measurement
-def _timed_steps(pkg, torch, Xs, maxdim, kw, steps, warmup, depth, host_in, dev_index, coalesce=1):
+def _timed_steps(pkg, torch, Xs, maxdim, kw, steps, warmup, depth, host_in, dev_index, coalesce=1, last=None):
     """K steps (sequential, or through ripser.SweepPipeline: `depth` calls in flight on separate
     workspace slots, each call covering up to `coalesce` consecutive steps' sweeps) between two
-    syncs; step i runs sweep Xs[i % len(Xs)].  Returns (elapsed s, device ms per step)."""
+    syncs; step i runs sweep Xs[i % len(Xs)].  Returns (elapsed s, device ms per step); a
+    list passed as `last` receives the last step's result (its list of LayerResults)."""
     import collections
 
     dev_ms = []
     K = len(Xs)
 
     def done(res, info):
+        if last is not None:
+            last[:] = [res]
         if host_in:  # debug_tda_pipeline.py:110: dgms = result['dgms'] for every layer
             for r in res:
                 r.dgms
@@ -416,11 +427,13 @@ def stage_roofline(run, name: str, X, Lk: int, n: int, d: int, maxdim: int, kw: 
     }
 
 
-def measure(pkg, torch, dev, name: str, steps: int, warmup: int, layers: int | None = None) -> dict:
+def measure(pkg, torch, dev, name: str, steps: int, warmup: int, layers: int | None = None, full: bool = True) -> dict:
+    """One workload's record.  `full` False (a plain run): the timed steps alone -- no one-call-at-a-time
+    pass next to a pipelined figure and no stage pass (roofline, stages_ms)."""
     L, maxdim, desc, _, _ = WORKLOADS[name]
     L = layers or L
     if name.startswith("ripser"):
-        return measure_dropin(pkg, torch, name, steps, warmup, L)
+        return measure_dropin(pkg, torch, name, steps, warmup, L, full)
     sweeps = workload_sweeps(name, L)
     X_host = sweeps[0]
     n, d = X_host.shape[1], X_host.shape[2]
@@ -440,10 +453,11 @@ def measure(pkg, torch, dev, name: str, steps: int, warmup: int, layers: int | N
     dev_index = dev.index if dev.index is not None else 0
     seq = None
     piped = depth > 1 or coalesce > 1
+    last = []
     # TDA_BENCH_STAGE_ONLY=1 (profiling): only the stage pass below runs, so a rocprof trace of the
     # command holds exactly the launches the roofline's kernel_avg_ms is taken from (profiles/*_stage.csv)
-    stage_only = os.environ.get("TDA_BENCH_STAGE_ONLY") == "1"
-    if piped and os.environ.get("TDA_BENCH_NO_SEQ") != "1" and not stage_only:  # the one-call-at-a-time figure next to the pipelined one
+    stage_only = full and os.environ.get("TDA_BENCH_STAGE_ONLY") == "1"
+    if full and piped and os.environ.get("TDA_BENCH_NO_SEQ") != "1" and not stage_only:  # the one-call-at-a-time figure next to the pipelined one
         # (TDA_BENCH_NO_SEQ=1: profiling runs, so every launch in the trace is the pipeline's batch)
         el_s, dm_s = _timed_steps(pkg, torch, Xs, maxdim, kw, steps, warmup, 1, host_in, dev_index)
         seq = {"value": L * steps / el_s, "ms_per_step": el_s / steps * 1e3, "device_ms_per_step": sum(dm_s) / len(dm_s)}
@@ -451,12 +465,15 @@ def measure(pkg, torch, dev, name: str, steps: int, warmup: int, layers: int | N
         el, dev_ms = float("nan"), [float("nan")]
     else:
         el, dev_ms = _timed_steps(pkg, torch, Xs, maxdim, kw_pipe if piped else kw, steps, warmup, depth, host_in, dev_index,
-                                  coalesce)
+                                  coalesce, last)
     # per-kernel durations after the timed region, same batch (a coalesced pipeline launches every
     # kernel over `coalesce` sweeps: the stage pass runs that batch too)
-    Xst, Lk = ([Xs[i % len(Xs)] for i in range(coalesce)], L * coalesce) if coalesce > 1 else (Xs[0], L)
-    sr = stage_roofline(pkg.ripser_batch, name, Xst, Lk, n, d, maxdim, kw, max(1, min(steps, 10)))
+    sr = {"roofline": None, "roofline_mfma": None, "stages_ms": None}
+    if full:
+        Xst, Lk = ([Xs[i % len(Xs)] for i in range(coalesce)], L * coalesce) if coalesce > 1 else (Xs[0], L)
+        sr = stage_roofline(pkg.ripser_batch, name, Xst, Lk, n, d, maxdim, kw, max(1, min(steps, 10)))
     return {
+        "last": last[0] if last else None,
         "value": L * steps / el, "unit": "layers/s", "ms_per_step": el / steps * 1e3, "steps": steps, "warmup": warmup,
         "device_ms_per_step": sum(dev_ms) / len(dev_ms), "X_host": np.concatenate(sweeps), "maxdim": maxdim,
         "config": {"workload": desc, "layers_per_gpu_step": L, "n_points": int(n), "dim": int(d), "maxdim": maxdim,
@@ -470,7 +487,7 @@ def measure(pkg, torch, dev, name: str, steps: int, warmup: int, layers: int | N
     }
 
 
-def measure_dropin(pkg, torch, name: str, steps: int, warmup: int, L: int) -> dict:
+def measure_dropin(pkg, torch, name: str, steps: int, warmup: int, L: int, full: bool = True) -> dict:
     """The drop-in at the reference's own call: a step is the reference's
     layer loop -- ``result = ripser(cloud, maxdim=1); dgms = result['dgms']`` for each of the L
     layers, one call per layer (debug_tda_pipeline.py:109-110; analyze_adversarial_tda.py:100):
@@ -483,13 +500,17 @@ def measure_dropin(pkg, torch, name: str, steps: int, warmup: int, L: int) -> di
         pkg.ripser(X[i % L], maxdim=maxdim)["dgms"]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = [None] * L
     for _ in range(steps):
         for l in range(L):
-            dgms = pkg.ripser(X[l], maxdim=maxdim)["dgms"]  # noqa: F841  (the reference reads result['dgms'])
+            last[l] = pkg.ripser(X[l], maxdim=maxdim)["dgms"]  # the reference reads result['dgms']
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
-    sr = stage_roofline(pkg.ripser_batch, name, X[:1], 1, n, d, maxdim, {}, 10)
+    sr = {"roofline": None, "roofline_mfma": None, "stages_ms": None}
+    if full:
+        sr = stage_roofline(pkg.ripser_batch, name, X[:1], 1, n, d, maxdim, {}, 10)
     return {
+        "last": last,
         "value": L * steps / el, "unit": "layers/s", "ms_per_step": el / steps * 1e3, "steps": steps, "warmup": warmup,
         "ms_per_call": el / (steps * L) * 1e3, "device_ms_per_step": None, "X_host": X, "maxdim": maxdim,
         "config": {"workload": desc, "layers_per_gpu_step": L, "n_points": int(n), "dim": int(d), "maxdim": maxdim,
@@ -523,6 +544,43 @@ def measure_umap(pkg, torch, dev, steps: int = 10, warmup: int = 2) -> dict:
             "config": {"workload": UMAP_DESC, "layers_per_gpu_step": 32, "n_points": 36, "dim": 4096},
             "data": DATA["raw4096"], "roofline": None,
             "cpu_baseline": None, "note": "umap-learn is not installed here (no CPU reference to time); layout parity unpinned"}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, last, maxdim: int) -> None:
+    """``--dump-outputs DIR``: what the last timed step returned to its caller -- every layer's
+    ``dgms`` list -- as float64 .npy files:
+      dgms_counts.npy   (L, maxdim + 1): pairs of layer l in dimension k
+      dgm<k>.npy        (n, 4), n > 0: one row per pair of dimension k, layers in layer order and
+                        pairs in the order the call returned them: layer, birth, death, infinite.
+                        A class that never dies (death +inf) has infinite = 1 and its birth in the
+                        death column, so every stored value is finite and two builds' files can
+                        be subtracted (a finite pair never has death == birth)
+    A dimension without a pair in any layer writes no file: its column of dgms_counts is zero.
+    The inputs are seeded (synthetic.py), so the same arguments give the same files.  Arrays that
+    would pass 64 MB in all are cut to a fixed, seeded sample of their rows; dgms_counts then
+    still counts the whole output, and the layer column says where each kept row belongs."""
+    os.makedirs(path, exist_ok=True)
+    dg = [[np.asarray(d, dtype=np.float64).reshape(-1, 2) for d in (r.dgms if hasattr(r, "dgms") else r)] for r in last]
+    arrays = {"dgms_counts": np.array([[len(d) for d in layer] for layer in dg], dtype=np.float64)}
+    for k in range(maxdim + 1):
+        rows = np.concatenate([layer[k] for layer in dg])
+        if not len(rows):
+            continue
+        lay = np.concatenate([np.full(len(layer[k]), l, dtype=np.float64) for l, layer in enumerate(dg)])
+        inf = ~np.isfinite(rows[:, 1])
+        arrays[f"dgm{k}"] = np.stack([lay, rows[:, 0], np.where(inf, rows[:, 0], rows[:, 1]), inf.astype(np.float64)], axis=1)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:  # the same rows of every run: a seeded choice, in order, at least one row each
+        keep = DUMP_MAX_BYTES / total * 0.95
+        rng = np.random.default_rng(0)
+        for name in [a for a in arrays if a != "dgms_counts"]:
+            n = len(arrays[name])
+            arrays[name] = arrays[name][np.sort(rng.choice(n, max(1, int(n * keep)), replace=False))]
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def _free_port() -> int:
@@ -611,6 +669,13 @@ def main():
                     help="secondary workloads measured at N=1 (comma list, '' for none)")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything next to the headline figure: the CPU baselines (unless --no-cpu), the --extra workloads, "
+                         "the one-call-at-a-time pass, the stage pass (roofline, stages_ms) and, at --gpus N > 1, the "
+                         "strong-scaling record.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64): "
+                         "every layer's diagrams, see dump_outputs (one GPU only)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: every rank runs its own L-layer batch; strong: the L layers are sharded over ranks")
     args = ap.parse_args()
@@ -618,6 +683,16 @@ def main():
         args.steps = WORKLOADS[args.workload][3]
     if args.warmup is None:
         args.warmup = WORKLOADS[args.workload][4]
+
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", 1)) > 1):
+        ap.error("--dump-outputs writes one GPU's last step: use --gpus 1")
+    if os.environ.get("TDA_BENCH_STAGE_ONLY") == "1":
+        if not args.full:
+            ap.error("TDA_BENCH_STAGE_ONLY=1 runs the stage pass alone, which is part of --full")
+        if args.dump_outputs:
+            ap.error("TDA_BENCH_STAGE_ONLY=1 skips the timed steps: there is no last step for --dump-outputs")
+    if not args.full:  # a plain run: the headline figure alone
+        args.no_cpu, args.extra = True, ""
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         cpu_file = parent_cpu_baseline(args)  # before any process touches the GPU
@@ -678,8 +753,11 @@ def main():
     L = args.layers or L
     prim, strong, multi_roof = None, None, None
     if world == 1:
-        prim = measure(pkg, torch, dev, args.workload, args.steps, args.warmup, args.layers)
+        prim = measure(pkg, torch, dev, args.workload, args.steps, args.warmup, args.layers, args.full)
         value, el_ms = prim["value"], prim["ms_per_step"]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, prim["last"], prim["maxdim"])
+        prim["last"] = None
     else:
         host_in = args.workload.endswith("_host")
         sweeps = workload_sweeps(args.workload, L)
@@ -719,10 +797,11 @@ def main():
         el = run_multi(args.scaling == "strong")
         value = (L if args.scaling == "strong" else L * world) * args.steps / el
         el_ms = el / args.steps * 1e3
-        el_s = run_multi(True) if args.scaling == "weak" else el
-        strong = {"value": L * args.steps / el_s, "unit": "layers/s", "ms_per_step": el_s / args.steps * 1e3,
-                  "scaling": "strong", "layers_total": L, "layers_per_gpu": -(-L // world)}
-        if rank == 0:
+        if args.full or args.scaling == "strong":  # a plain weak run skips the strong-scaling pass of its own
+            el_s = run_multi(True) if args.scaling == "weak" else el
+            strong = {"value": L * args.steps / el_s, "unit": "layers/s", "ms_per_step": el_s / args.steps * 1e3,
+                      "scaling": "strong", "layers_total": L, "layers_per_gpu": -(-L // world)}
+        if rank == 0 and args.full:
             # the line's roofline: rank 0's own GPU, the weak step's per-rank batch (the same stage pass as the
             # one-GPU record), after every rank's timed region
             Lk = L * coalesce if coalesce > 1 else L
@@ -761,7 +840,8 @@ def main():
             if prim.get("roofline_mfma"):
                 out["roofline_mfma"] = prim["roofline_mfma"]
             out["device_ms_per_step"] = prim["device_ms_per_step"]
-            out["stages_ms"] = prim["stages_ms"]
+            if prim["stages_ms"] is not None:
+                out["stages_ms"] = prim["stages_ms"]
             out["pipeline"] = prim["pipeline"]
         elif multi_roof:
             out["stages_ms"] = multi_roof["stages_ms"]
@@ -781,7 +861,7 @@ def main():
             out["speedup_vs_cpu"] = speedups(value, cb, args.workload)
             if strong:
                 strong["speedup_vs_cpu"] = speedups(strong["value"], cb, args.workload)
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         cpu_done = {}
         if do_cpu:
             cb = cpu_baseline(pool, P, args.workload, prim["X_host"], prim["maxdim"], args.cpu_seconds)
@@ -818,7 +898,7 @@ def main():
         pool.close()
         pool.join()
     if rank == 0:
-        if world == 1:
+        if world == 1 and args.full:
             out["summary"] = summary(out)  # last key: the driver keeps the tail of the line
         print(json.dumps(out), flush=True)
     if dist is not None:

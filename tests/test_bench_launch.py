@@ -20,7 +20,7 @@ def test_bench_gpus2_starts_two_ranks_cpu_rehearsal():
                PYTHONPATH=ROOT)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "sweep48", "--layers", "4",
-                        "--steps", "2", "--warmup", "1", "--cpu-seconds", "1"], cwd=ROOT, env=env, capture_output=True, text=True,
+                        "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--full"], cwd=ROOT, env=env, capture_output=True, text=True,
                        timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

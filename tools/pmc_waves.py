@@ -48,10 +48,12 @@ def parse(d):
 def main():
     if sys.argv[1] == "run":
         wl = sys.argv[2]
-        d = f"gpurun_out/pmcw_{wl}"
+        out = os.environ.get("OUT", "bench_out")  # as the shell tools: where the run's files go
+        os.makedirs(out, exist_ok=True)
+        d = f"{out}/pmcw_{wl}"
         cmd = ["timeout", "-s", "KILL", "120", "rocprofv3", "--pmc", *CTRS, "--output-format", "csv", "-d", d, "-o", "run", "--",
-               "python3", "bench.py", "--workload", wl, "--steps", "5", "--warmup", "1", "--no-cpu", "--extra", ""]
-        with open(f"gpurun_out/pmcw_{wl}.txt", "w") as log:
+               "python3", "bench.py", "--full", "--workload", wl, "--steps", "5", "--warmup", "1", "--no-cpu", "--extra", ""]
+        with open(f"{out}/pmcw_{wl}.txt", "w") as log:
             rc = subprocess.call(cmd, stdout=log, stderr=subprocess.STDOUT)
         if rc:
             print("rocprofv3 rc", rc)
