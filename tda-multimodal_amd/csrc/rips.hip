@@ -30,6 +30,7 @@
 #include "rips_reduce_big.h"
 #include "rips_reduce_par.h"
 #include "rips_reduce_small.h"
+#include "rips_retry.h"
 
 using namespace tda;
 
@@ -217,9 +218,9 @@ ReduceAllCfg reduce_cfg(int n, int maxdim, const uint64_t* piv_words, bool lds_m
     return c;
 }
 
-constexpr int kMaxParScale = 4;  // k_reduce_par capacity retries: pools up to 16x
-// no_par: 0 = k_reduce_par for H1 and H2, 1 = H1 only (an H2 launch aborted), 2 = none
-int make_plan(Plan& p, bool force_global, int scale, bool force_big, int no_par) {
+int make_plan(Plan& p, const Attempt& at) {
+    const bool force_global = at.force_global, force_big = at.force_big;
+    const int scale = at.scale, no_par = at.no_par;
     const uint64_t N = (uint64_t)p.N, L = (uint64_t)p.L;
     p.mst_words = (binom(N, 2) + 31) / 32 + 1;
     for (int d = 1; d <= p.maxdim; ++d) {
@@ -512,9 +513,7 @@ struct Workspace {
     struct Retry {
         int64_t N;
         int maxdim, input_kind;
-        bool force_global, force_big;
-        int no_par;
-        int scale;
+        Attempt at;  // no_cap stays false: column caps are not remembered
     };
     std::vector<Retry> retry;
     std::mutex mu;
@@ -954,20 +953,25 @@ void splice_layers(ResultImpl& R, const std::vector<int>& ls, const std::vector<
     point_result(R, total);
 }
 
-int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev, tda_rips_result** out,
-                 bool force_global, int scale, bool force_big, int no_par, bool no_cap);
+#include "rips_enqueue.h"
+#if defined(TDA_PROFILE) || defined(TDA_PROF2)
+#include "rips_prof.h"
+#endif
+
+int run_attempts(const tda_rips_args& a, int input_kind, const void* src, tda_rips_result** out, Attempt at);
 
 // Column caps missed on some layers (ERR_CAP_MISS: a column's pivot lies above its cap -- a
 // class that lives longer than capf * thresh, e.g. the one loop of a circle): each such layer is
 // re-run ALONE without caps and spliced into the batch's result; the other layers keep their
 // capped (exact) reductions.  A one-layer call simply re-runs without caps.
 int rerun_cap_missed(const tda_rips_args& a, int input_kind, const void* host_or_dev, tda_rips_result** out, ResultImpl* R,
-                     const std::vector<int>& ls, bool force_global, int scale, bool force_big, int no_par) {
+                     const std::vector<int>& ls, Attempt at) {
     std::unique_ptr<ResultImpl> own(R);
+    at.no_cap = true;
     if (getenv("TDA_DEBUG")) fprintf(stderr, "[tda] column cap missed on %zu of %lld layers: re-run without caps\n", ls.size(), (long long)a.L);
     if (a.L == 1 || input_kind == 2) {
         const double dms = R->pub.device_ms;
-        if (int rc = run_pipeline(a, input_kind, host_or_dev, out, force_global, scale, force_big, no_par, true)) return rc;
+        if (int rc = run_attempts(a, input_kind, host_or_dev, out, at)) return rc;
         (*out)->n_cap_reruns = a.L;
         (*out)->device_ms += dms;
         return 0;
@@ -996,7 +1000,7 @@ int rerun_cap_missed(const tda_rips_args& a, int input_kind, const void* host_or
         b.n_label_sets = 0;
         b.want_twonn = 0;
         tda_rips_result* sub = nullptr;
-        if (int rc = run_pipeline(b, input_kind, b.x, &sub, force_global, scale, force_big, no_par, true)) return rc;
+        if (int rc = run_attempts(b, input_kind, b.x, &sub, at)) return rc;
         subs.push_back(sub);
         dms += sub->device_ms;
     }
@@ -1007,877 +1011,208 @@ int rerun_cap_missed(const tda_rips_args& a, int input_kind, const void* host_or
     return 0;
 }
 
-// input_kind: 0 = points (dtype), 1 = square distance (dtype), 2 = condensed f32
-// no_cap: k_reduce_par without column caps (a capped column ran empty below its cap: code 81)
-int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev, tda_rips_result** out,
-                 bool force_global, int scale, bool force_big, int no_par, bool no_cap) {
-    const auto h_entry = std::chrono::steady_clock::now();
-    Plan p;
-    p.L = a.L;
-    p.N = a.N;
-    p.D = a.D;
-    p.maxdim = a.maxdim;
-    p.dtype = a.dtype;
-    p.is_dist = input_kind != 0;
-    p.want64 = input_kind == 0 && a.dtype == TDA_F64 && a.want_dist && (a.flags & TDA_FLAG_DIST64);
-    make_plan(p, force_global, scale, force_big, no_par);
-    const int dev = a.device;
-    HIPC(hipSetDevice(dev));
-    Workspace& w = *get_ws(dev, a.slot);
-    std::unique_lock<std::mutex> guard(w.mu);  // released before any retry (which re-enters)
-    // allocations, frees and graph drops (first call / growth) never overlap another slot's
-    // capture: g_capture_mu is held from here through the buffer growth below, and released
-    // before the input copies (the host-input memcpy serialised pipelined slots)
-    std::unique_lock<std::mutex> rt_lock(g_capture_mu);
+// Grows one per-call buffer of the workspace to `need` elements of `elem` bytes (at least
+// `floor`).  baked: captured graphs hold its address, so they are dropped with it.  Mapped
+// buffers refresh their device pointer.  Called under g_capture_mu (a free synchronises the device).
+enum BufMem { kPinned, kMapped, kDevice };
+int grow_buf(Workspace& w, void** buf, size_t& cap, size_t need, size_t floor, size_t elem, BufMem mem, bool baked, void** dev_ptr) {
+    if (cap >= need) return 0;
+    if (baked) drop_graphs(w);
+    if (*buf) HIPC(mem == kDevice ? hipFree(*buf) : hipHostFree(*buf));
+    *buf = nullptr;
+    cap = 0;
+    const size_t want = std::max(need, floor);
+    if (mem == kDevice)
+        HIPC(hipMalloc(buf, want * elem));
+    else
+        HIPC(hipHostMalloc(buf, want * elem, mem == kMapped ? hipHostMallocMapped : hipHostMallocDefault));
+    if (mem == kMapped) HIPC(hipHostGetDevicePointer(dev_ptr, *buf, 0));
+    cap = want;
+    return 0;
+}
+
+// silhouette labels: every set must be codes 0..K-1, all used, 2 <= K <= n - 1 (sklearn); sil_K: the largest K
+int validate_labels(const tda_rips_args& a, int n, int nls, int& sil_K) {
+    for (int q = 0; q < nls; ++q) {
+        int K = 0;
+        std::vector<int> f(kSilMaxK, 0);
+        for (int i = 0; i < n; ++i) {
+            const int32_t c = a.labels[(size_t)q * n + i];
+            if (c < 0 || c >= kSilMaxK) return fail(TDA_E_INVALID, "silhouette labels must be codes 0..K-1 with K <= 32");
+            ++f[c];
+            K = std::max(K, c + 1);
+        }
+        for (int c = 0; c < K; ++c)
+            if (!f[c]) return fail(TDA_E_INVALID, "silhouette labels must be contiguous codes 0..K-1 (LabelEncoder)");
+        if (K < 2 || K > n - 1)
+            return fail(TDA_E_INVALID, "Number of labels is " + std::to_string(K) + ". Valid values are 2 to n_samples - 1 (inclusive)");
+        sil_K = std::max(sil_K, K);
+    }
+    return 0;
+}
+
+// The workspace sized for this call's plan and arguments, and the call's view of it.  Allocations,
+// frees and graph drops (first call / growth) never overlap another slot's capture: the caller
+// holds g_capture_mu, and releases it before the input copies (the host-input memcpy
+// serialised pipelined slots).
+int prepare_buffers(Call& c) {
+    const tda_rips_args& a = c.a;
+    const Plan& p = c.p;
+    Workspace& w = c.w;
     if (int rc = ws_prepare(w, p)) return rc;
-    if (int rc = set_lds_attrs(dev)) return rc;
-    // all work runs on the library stream, ordered after the caller's stream
-    hipStream_t s = w.stream;
-    char* B = w.dbuf;
-    const int n = (int)p.N, L = (int)p.L;
-    float* dist = (float*)(B + p.o_dist);
-    LayerStats* stats = (LayerStats*)(B + p.o_stats);
-    const size_t esz = p.dtype == TDA_F64 ? 8 : 4;
-    PairSet ps = {};
+    if (int rc = set_lds_attrs(a.device)) return rc;
+    c.s = w.stream;
+    c.B = w.dbuf;
+    const int n = c.n = (int)p.N, L = c.L = (int)p.L;
+    c.dist = (float*)(c.B + p.o_dist);
+    c.stats = (LayerStats*)(c.B + p.o_stats);
+    c.rowmax = (uint32_t*)(c.B + p.o_rowmax);
+    c.esz = p.dtype == TDA_F64 ? 8 : 4;
     for (int d = 0; d <= p.maxdim; ++d) {
-        ps.p[d] = (Pair*)(B + p.o_pairs[d]);
-        ps.cap[d] = p.pcap[d];
+        c.ps.p[d] = (Pair*)(c.B + p.o_pairs[d]);
+        c.ps.cap[d] = p.pcap[d];
     }
 
     // host inputs go through a pinned staging buffer: a stable graph source
     // (grown here, filled after the lock is released)
-    const void* xsrc = host_or_dev;
-    const int nparts = input_kind == 2 ? 0 : a.n_parts;
-    const bool host_in = !a.x_on_device || input_kind == 2;
-    const bool dev_parts = !host_in && nparts > 0;
-    const size_t xbytes = input_kind == 2 ? binom((uint64_t)n, 2) * 4
-                                          : (size_t)L * n * (input_kind == 1 ? (size_t)n : (size_t)p.D) * esz;
+    c.xsrc = c.host_or_dev;
+    c.nparts = c.input_kind == 2 ? 0 : a.n_parts;
+    c.host_in = !a.x_on_device || c.input_kind == 2;
+    c.dev_parts = !c.host_in && c.nparts > 0;
+    c.xbytes = c.input_kind == 2 ? binom((uint64_t)n, 2) * 4
+                                 : (size_t)L * n * (c.input_kind == 1 ? (size_t)n : (size_t)p.D) * c.esz;
     // want_dist: the matrices come back by an async copy queued behind the call's work (one
     // stream sync for both; r06: a blocking hipMemcpy after the sync cost ~20 us per small call)
-    const size_t dbytes = a.want_dist ? (size_t)L * n * n * (4 + (p.want64 ? 8 : 0)) : 0;
-    if (dbytes > w.hdist_cap) {
-        if (w.hdist) HIPC(hipHostFree(w.hdist));
-        w.hdist = nullptr;
-        w.hdist_cap = 0;
-        HIPC(hipHostMalloc((void**)&w.hdist, std::max<size_t>(dbytes, 1 << 16), hipHostMallocDefault));
-        w.hdist_cap = std::max<size_t>(dbytes, 1 << 16);
-    }
-    if (host_in) {
-        if (w.hin_cap < xbytes) {
-            drop_graphs(w);
-            if (w.hin) HIPC(hipHostFree(w.hin));
-            w.hin = nullptr;
-            HIPC(hipHostMalloc((void**)&w.hin, std::max<size_t>(xbytes, 1 << 16), hipHostMallocDefault));
-            w.hin_cap = std::max<size_t>(xbytes, 1 << 16);
-        }
-        xsrc = w.hin;
-    } else if (dev_parts) {
-        if (w.xin_cap < xbytes) {
-            drop_graphs(w);
-            if (w.xin) HIPC(hipFree(w.xin));
-            w.xin = nullptr;
-            HIPC(hipMalloc(&w.xin, xbytes));
-            w.xin_cap = xbytes;
-        }
-        xsrc = w.xin;
+    c.dbytes = a.want_dist ? (size_t)L * n * n * (4 + (p.want64 ? 8 : 0)) : 0;
+    if (int rc = grow_buf(w, (void**)&w.hdist, w.hdist_cap, c.dbytes, 1 << 16, 1, kPinned, false, nullptr)) return rc;
+    if (c.host_in) {
+        if (int rc = grow_buf(w, (void**)&w.hin, w.hin_cap, c.xbytes, 1 << 16, 1, kPinned, true, nullptr)) return rc;
+        c.xsrc = w.hin;
+    } else if (c.dev_parts) {
+        if (int rc = grow_buf(w, &w.xin, w.xin_cap, c.xbytes, 0, 1, kDevice, true, nullptr)) return rc;
+        c.xsrc = w.xin;
     }
 
     // silhouette labels -> host-mapped buffer (stable address: a graph source)
-    const int nls = (a.labels && a.n_label_sets > 0) ? (int)a.n_label_sets : 0;
-    int sil_K = 0;
-    size_t sil_out_off = 0;
-    if (nls) {
-        for (int q = 0; q < nls; ++q) {
-            int K = 0;
-            std::vector<int> f(kSilMaxK, 0);
-            for (int i = 0; i < n; ++i) {
-                const int32_t c = a.labels[(size_t)q * n + i];
-                if (c < 0 || c >= kSilMaxK) return fail(TDA_E_INVALID, "silhouette labels must be codes 0..K-1 with K <= 32");
-                ++f[c];
-                K = std::max(K, c + 1);
-            }
-            for (int c = 0; c < K; ++c)
-                if (!f[c]) return fail(TDA_E_INVALID, "silhouette labels must be contiguous codes 0..K-1 (LabelEncoder)");
-            if (K < 2 || K > n - 1)
-                return fail(TDA_E_INVALID, "Number of labels is " + std::to_string(K) + ". Valid values are 2 to n_samples - 1 (inclusive)");
-            sil_K = std::max(sil_K, K);
-        }
-        sil_out_off = align_up((size_t)nls * n * 4, 16);
-        const size_t need = sil_out_off + (size_t)L * nls * 8;
-        if (w.hsil_cap < need) {
-            drop_graphs(w);
-            if (w.hsil) HIPC(hipHostFree(w.hsil));
-            w.hsil = nullptr;
-            HIPC(hipHostMalloc((void**)&w.hsil, std::max<size_t>(need, 1 << 12), hipHostMallocMapped));
-            HIPC(hipHostGetDevicePointer((void**)&w.hsil_dev, w.hsil, 0));
-            w.hsil_cap = std::max<size_t>(need, 1 << 12);
-        }
+    c.nls = (a.labels && a.n_label_sets > 0) ? (int)a.n_label_sets : 0;
+    if (c.nls) {
+        if (int rc = validate_labels(a, n, c.nls, c.sil_K)) return rc;
+        c.sil_out_off = align_up((size_t)c.nls * n * 4, 16);
+        const size_t need = c.sil_out_off + (size_t)L * c.nls * 8;
+        if (int rc = grow_buf(w, (void**)&w.hsil, w.hsil_cap, need, 1 << 12, 1, kMapped, true, (void**)&w.hsil_dev)) return rc;
     }
 
     // TwoNN estimates -> host-mapped buffer (stable address: a graph source)
-    const bool want_tn = a.want_twonn != 0;
-    const bool no_ph = (a.flags & TDA_FLAG_NO_PERSISTENCE) != 0;  // distances + side metrics only
-    if (want_tn && w.htn_cap < (size_t)L) {
-        drop_graphs(w);
-        if (w.htn) HIPC(hipHostFree(w.htn));
-        w.htn = nullptr;
-        HIPC(hipHostMalloc((void**)&w.htn, sizeof(float) * std::max(L, 64), hipHostMallocMapped));
-        HIPC(hipHostGetDevicePointer((void**)&w.htn_dev, w.htn, 0));
-        w.htn_cap = std::max(L, 64);
-    }
+    c.want_tn = a.want_twonn != 0;
+    c.no_ph = (a.flags & TDA_FLAG_NO_PERSISTENCE) != 0;
+    if (c.want_tn)
+        if (int rc = grow_buf(w, (void**)&w.htn, w.htn_cap, (size_t)L, 64, sizeof(float), kMapped, true, (void**)&w.htn_dev)) return rc;
 
     // TDA_FLAG_STAGE_SERIAL (with stage times) or TDA_FLAG_ONE_STREAM: every
     // stage on the main stream -- each pair of stage events then brackets one
     // kernel only, and a slot keeps to one hardware queue (several slots in
     // flight each get their own: SweepPipeline)
-    const bool serial_stages = ((a.flags & TDA_FLAG_STAGE_TIMES) && (a.flags & TDA_FLAG_STAGE_SERIAL)) || (a.flags & TDA_FLAG_ONE_STREAM);
-    if (!serial_stages)
+    c.serial_stages = ((a.flags & TDA_FLAG_STAGE_TIMES) && (a.flags & TDA_FLAG_STAGE_SERIAL)) || (a.flags & TDA_FLAG_ONE_STREAM);
+    if (!c.serial_stages)
         if (int rc = ws_side_streams(w)) return rc;
+    return 0;
+}
 
-    rt_lock.unlock();  // buffers are in place; the capture below re-takes it
-
-    // input copies and ordering, outside the lock
-    if (a.x_on_device && input_kind != 2 && !(a.flags & TDA_FLAG_INPUT_READY))
-        if (int rc = order_after_caller(s, w.evin, a.stream, dev)) return rc;
-    if (host_in) {
-        if (nparts > 0) {  // parts: one after the other into the staging buffer
-            const size_t pb = xbytes / nparts;
-            for (int i = 0; i < nparts; ++i) std::memcpy((char*)w.hin + i * pb, a.x_parts[i], pb);
-        } else if (xbytes) {
-            std::memcpy(w.hin, host_or_dev, xbytes);
+// input copies and ordering, outside g_capture_mu
+int stage_inputs(Call& c) {
+    const tda_rips_args& a = c.a;
+    Workspace& w = c.w;
+    if (a.x_on_device && c.input_kind != 2 && !(a.flags & TDA_FLAG_INPUT_READY))
+        if (int rc = order_after_caller(c.s, w.evin, a.stream, a.device)) return rc;
+    if (c.host_in) {
+        if (c.nparts > 0) {  // parts: one after the other into the staging buffer
+            const size_t pb = c.xbytes / c.nparts;
+            for (int i = 0; i < c.nparts; ++i) std::memcpy((char*)w.hin + i * pb, a.x_parts[i], pb);
+        } else if (c.xbytes) {
+            std::memcpy(w.hin, c.host_or_dev, c.xbytes);
         }
-    } else if (dev_parts) {
+    } else if (c.dev_parts) {
         // device parts: gathered into the workspace's own input buffer by one kernel on the
         // library stream (ordered after the caller's stream above, outside any captured graph)
         PartList pl = {};
-        for (int i = 0; i < nparts; ++i) pl.p[i] = a.x_parts[i];
-        const uint64_t words = xbytes / nparts / 4;
+        for (int i = 0; i < c.nparts; ++i) pl.p[i] = a.x_parts[i];
+        const uint64_t words = c.xbytes / c.nparts / 4;
         const unsigned gx = (unsigned)std::min<uint64_t>(64, (words + 255) / 256);
-        hipLaunchKernelGGL(k_gather_parts, dim3(std::max(1u, gx), nparts), dim3(256), 0, s, pl, words, (uint32_t*)w.xin);
+        hipLaunchKernelGGL(k_gather_parts, dim3(std::max(1u, gx), c.nparts), dim3(256), 0, c.s, pl, words, (uint32_t*)w.xin);
         HIPC(hipGetLastError());
     }
-    if (nls) std::memcpy(w.hsil, a.labels, (size_t)nls * n * 4);
+    if (c.nls) std::memcpy(w.hsil, a.labels, (size_t)c.nls * c.n * 4);
+    return 0;
+}
 
-    // serial_stages: the side streams are aliased to the main one here and restored on return
-    struct StreamSwap {
-        Workspace& w;
-        hipStream_t s2, s3, s4;
-        bool on;
-        ~StreamSwap() {
-            if (on) w.stream2 = s2, w.stream3 = s3, w.stream4 = s4;
-        }
-    } swap_guard{w, w.stream2, w.stream3, w.stream4, serial_stages};
-    if (serial_stages) w.stream2 = w.stream3 = w.stream4 = s;
-    StageTimer tm{w.stage_ev, s, (a.flags & TDA_FLAG_STAGE_TIMES) != 0, {}};
-    StageTimer tm2{w.stage_ev2, w.stream2, tm.on, {}};
-    StageTimer tm3{w.stage_ev3, w.stream3, tm.on, {}};
-    StageTimer tm4{w.stage_ev4, w.stream4, tm.on, {}};
-    if (serial_stages) tm2.fwd = tm3.fwd = tm4.fwd = &tm;
+// serial_stages: the side streams are aliased to the main one for the call and restored on return
+struct StreamSwap {
+    Workspace& w;
+    hipStream_t s2, s3, s4;
+    bool on;
+    ~StreamSwap() {
+        if (on) w.stream2 = s2, w.stream3 = s3, w.stream4 = s4;
+    }
+};
+
+// what a captured launch sequence depends on; also settles the two switches that are part of it
+void fill_graph_key(Call& c, GraphKey& gk) {
+    const tda_rips_args& a = c.a;
+    const Plan& p = c.p;
     // D >= 32 (raw activations): Gram tiles on the FP64 matrix cores; TDA_DIST=scalar|mfma forces one (tests)
-    const bool dist_mfma = input_kind == 0 && (test_env_is("TDA_DIST", "mfma") || (p.D >= kDistMfmaMinD && !test_env_is("TDA_DIST", "scalar")));
-    GraphKey gk;
+    c.dist_mfma = c.input_kind == 0 && (test_env_is("TDA_DIST", "mfma") || (p.D >= kDistMfmaMinD && !test_env_is("TDA_DIST", "scalar")));
+    // column caps only with ripser's default threshold (the enclosing radius: no essential
+    // H1 / H2 class); a finite user threshold can leave classes essential (k_reduce_par)
+    // caps also off when H2 runs on the serial k_reduce_big after a parallel H1 (TDA_PAR2=0, or an H2
+    // abort): that kernel reads every layer's H1 pivots, so no layer's H1 may be left unfinished
+    const bool h2_serial = p.par && p.maxdim >= 2 && !p.par2;
+    c.capf = (c.at.no_cap || h2_serial || !(std::isinf(a.thresh) || a.thresh == 3.402823466e+38f)) ? 0.0f : par_capf();
     std::memset(&gk, 0, sizeof(gk));
     gk.L = p.L;
     gk.N = p.N;
     gk.D = p.D;
     gk.maxdim = p.maxdim;
     gk.dtype = p.dtype;
-    gk.input_kind = input_kind;
+    gk.input_kind = c.input_kind;
     gk.x_on_device = a.x_on_device;
     gk.flags = a.flags;
-    gk.force_global = force_global;
-    gk.scale = scale;
-    gk.force_big = force_big;
-    gk.no_par = no_par;
-    gk.no_cap = no_cap;
-    // column caps only with ripser's default threshold (the enclosing radius: no essential
-    // H1 / H2 class); a finite user threshold can leave classes essential (k_reduce_par)
-    // caps also off when H2 runs on the serial k_reduce_big after a parallel H1 (TDA_PAR2=0, or an H2
-    // abort): that kernel reads every layer's H1 pivots, so no layer's H1 may be left unfinished
-    const bool h2_serial = p.par && p.maxdim >= 2 && !p.par2;
-    const float capf = (no_cap || h2_serial || !(std::isinf(a.thresh) || a.thresh == 3.402823466e+38f)) ? 0.0f : par_capf();
-    gk.capf = capf;
-    gk.variant = (p.dense ? 1 : 0) | (p.big ? 2 : 0) | (p.fast ? 4 : 0) | (p.lds_mode ? 8 : 0) | (p.cmode << 4) | (p.par ? 1 << 8 : 0) | (dist_mfma ? 1 << 9 : 0) |
+    gk.force_global = c.at.force_global;
+    gk.scale = c.at.scale;
+    gk.force_big = c.at.force_big;
+    gk.no_par = c.at.no_par;
+    gk.no_cap = c.at.no_cap;
+    gk.capf = c.capf;
+    gk.variant = (p.dense ? 1 : 0) | (p.big ? 2 : 0) | (p.fast ? 4 : 0) | (p.lds_mode ? 8 : 0) | (p.cmode << 4) | (p.par ? 1 << 8 : 0) | (c.dist_mfma ? 1 << 9 : 0) |
                  (p.wide ? 1 << 10 : 0) | (p.want64 ? 1 << 11 : 0) | (p.par2 ? 1 << 12 : 0) | (p.piv2_sparse ? 1 << 13 : 0);
     gk.thresh = a.thresh;
-    gk.n_label_sets = nls;
-    gk.sil_K = sil_K;  // baked into the k_silhouette launch (argument K and its LDS size)
-    gk.twonn = want_tn;
-    gk.tn_discard = want_tn ? a.twonn_discard : 0.0;
-    gk.tn_eps = want_tn ? a.twonn_eps : 0.0f;
-    gk.x = xsrc;
-    gk.gen = w.gen;
+    gk.n_label_sets = c.nls;
+    gk.sil_K = c.sil_K;  // baked into the k_silhouette launch (argument K and its LDS size)
+    gk.twonn = c.want_tn;
+    gk.tn_discard = c.want_tn ? a.twonn_discard : 0.0;
+    gk.tn_eps = c.want_tn ? a.twonn_eps : 0.0f;
+    gk.x = c.xsrc;
+    gk.gen = c.w.gen;
+}
+
+// The call's launch sequence on the device: a replay of the graph captured for this key, else a
+// capture (instantiated, kept and launched), else -- stage-timed calls, TDA_GRAPH=0 -- eagerly.
+int launch_or_capture(Call& c, const GraphKey& gk) {
+    Workspace& w = c.w;
+    hipStream_t s = c.s;
     GraphEntry* ge = nullptr;
     // stage-timed calls run eagerly: timing events inside a capture need
     // external event nodes, which torch's bundled HIP runtime rejects
-    const bool use_graph = !test_env_is("TDA_GRAPH", "0") && !tm.on;
+    const bool use_graph = !test_env_is("TDA_GRAPH", "0") && !c.tm.on;
     if (use_graph)
         for (auto& g : w.graphs)
             if (g.key == gk) ge = &g;
-    const bool capture = use_graph && !ge;
-    // ev0 / ev1 bracket the whole sequence; a graph replay records them around the launch
-    auto rec_t = [&](hipEvent_t e) { return capture ? hipSuccess : hipEventRecord(e, s); };
-#define MARK(name) \
-    do {           \
-        if (int rc_ = tm.mark(name)) return rc_; \
-    } while (0)
-    auto enqueue = [&]() -> int {
-    HIPC(rec_t(w.ev0));
-    if (int rc = tm.begin()) return rc;
-    MARK("event_gap");  // an empty interval: what two back-to-back events measure with no kernel between (bench.py subtracts it)
-    HIPC(hipMemsetAsync(B + p.memset_lo, 0, p.memset_hi - p.memset_lo, s));
-    MARK("memset");
-
-    // ---- distances (+ row maxima for the enclosing radius)
-    uint32_t* rowmax = (uint32_t*)(B + p.o_rowmax);
-    if (input_kind == 0) {
-        const void* x = xsrc;
-        if (!a.x_on_device) {
-            HIPC(hipMemcpyAsync(B + p.o_x, x, (size_t)L * n * p.D * esz, hipMemcpyHostToDevice, s));
-            x = B + p.o_x;
-        }
-        dim3 grid((n + 15) / 16, (n + 15) / 16, L);
-        const bool mfma = dist_mfma;
-        const unsigned nt = (unsigned)((n + kDmT - 1) / kDmT);
-        double* gpart = (double*)(B + p.o_gpart);
-        double* npart = (double*)(B + p.o_npart);
-        double* d64 = p.want64 ? (double*)(B + p.o_d64) : nullptr;
-        const dim3 gsplit(nt * (nt + 1) / 2, L, (unsigned)p.dsplit);
-        const dim3 gcomb((unsigned)std::min<uint64_t>(1024, ((uint64_t)n * n + 255) / 256), L);
-        if (mfma && p.dsplit > 1 && p.dtype == TDA_F64) {
-            hipLaunchKernelGGL((k_distance_mfma<double, 0, true>), gsplit, dim3(256), 0, s, (const double*)x, n, (int)p.D, dist, rowmax,
-                               gpart, npart, (double*)nullptr);
-            hipLaunchKernelGGL((k_distance_combine<double, 0>), gcomb, dim3(256), 0, s, gpart, npart, p.dsplit, n, dist, rowmax, d64);
-            hipLaunchKernelGGL(k_rowmax, dim3((n + 3) / 4, L), dim3(256), 0, s, dist, n, rowmax);
-        } else if (mfma && (p.dsplit > 1 || p.gram_layer)) {
-            if (p.gram_layer)
-                hipLaunchKernelGGL(k_gram_layer, dim3((unsigned)p.dsplit, L), dim3(256), 0, s, (const float*)x, n, (int)p.D, gpart, npart);
-            else
-                hipLaunchKernelGGL((k_distance_mfma<float, 0, true>), gsplit, dim3(256), 0, s, (const float*)x, n, (int)p.D, dist, rowmax,
-                                   gpart, npart);
-            MARK(p.gram_layer ? "k_gram_layer" : "k_distance_mfma");  // the Gram kernel alone (bench roofline): combine, row maxima: own stages
-            hipLaunchKernelGGL((k_distance_combine<float, 0>), gcomb, dim3(256), 0, s, gpart, npart, p.dsplit, n, dist, rowmax);
-            MARK("k_distance_combine");
-            hipLaunchKernelGGL(k_rowmax, dim3((n + 3) / 4, L), dim3(256), 0, s, dist, n, rowmax);
-        } else if (mfma && p.dtype == TDA_F64)
-            hipLaunchKernelGGL((k_distance_mfma<double>), dim3(nt * (nt + 1) / 2, L), dim3(256), 0, s, (const double*)x, n, (int)p.D,
-                               dist, rowmax, (double*)nullptr, (double*)nullptr, d64);
-        else if (mfma)
-            hipLaunchKernelGGL((k_distance_mfma<float>), dim3(nt * (nt + 1) / 2, L), dim3(256), 0, s, (const float*)x, n, (int)p.D,
-                               dist, rowmax, (double*)nullptr, (double*)nullptr);
-        else if (p.dtype == TDA_F64)
-            hipLaunchKernelGGL(k_distance<double>, grid, dim3(256), 0, s, (const double*)x, n, (int)p.D, dist, rowmax, d64);
-        else
-            hipLaunchKernelGGL(k_distance<float>, grid, dim3(256), 0, s, (const float*)x, n, (int)p.D, dist, rowmax);
-    } else {
-        const void* x = xsrc;
-        unsigned gx = (unsigned)std::min<uint64_t>(1024, ((uint64_t)n * n + 255) / 256);
-        if (input_kind == 1) {
-            if (!a.x_on_device) {
-                HIPC(hipMemcpyAsync(B + p.o_x, x, (size_t)L * n * n * esz, hipMemcpyHostToDevice, s));
-                x = B + p.o_x;
-            }
-            if (p.dtype == TDA_F64)
-                hipLaunchKernelGGL(k_square_dist<double>, dim3(gx, L), dim3(256), 0, s, (const double*)x, n, dist);
-            else
-                hipLaunchKernelGGL(k_square_dist<float>, dim3(gx, L), dim3(256), 0, s, (const float*)x, n, dist);
-        } else {
-            const uint64_t ne = binom((uint64_t)n, 2);
-            if (ne) HIPC(hipMemcpyAsync(B + p.o_x, x, ne * 4, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_square_from_condensed, dim3(gx), dim3(256), 0, s, (const float*)(B + p.o_x), n, dist);
-        }
-        HIPC(hipGetLastError());
-        hipLaunchKernelGGL(k_rowmax, dim3((n + 3) / 4, L), dim3(256), 0, s, dist, n, rowmax);
-    }
-    HIPC(hipGetLastError());
-    MARK(input_kind != 0 ? "k_square_dist" : dist_mfma ? ((p.dsplit > 1 || p.gram_layer) && p.dtype == TDA_F32 ? "k_rowmax" : "k_distance_mfma") : "k_distance");
-    HIPC(hipEventRecord(w.evf, s));  // fork point of the side streams
-
-    DenseBufs dnb = {};
-
-    // ---- H0 on its own stream: it overlaps the apparent-pair kernels, which
-    // do not need the spanning forest (a forest edge is an H0 death, never an
-    // apparent column; the reductions skip forest edges among the residuals).
-    // The triangle ranks of the dense H1 chain go on a second side stream.
-    // Enqueued after apparent<1>, so the critical path's kernels are queued first.
-    auto launch_side = [&]() -> int {
-        hipStream_t s2 = w.stream2, s4 = w.stream4;
-        HIPC(hipStreamWaitEvent(s2, w.evf, 0));
-        HIPC(hipStreamWaitEvent(s4, w.evf, 0));
-        if (int rc = tm2.begin()) return rc;
-        if (int rc = tm4.begin()) return rc;
-        if (no_ph) {
-            // TDA_FLAG_NO_PERSISTENCE: no spanning forest, no H0 pairs
-        } else if (n <= kSmallN) {
-            hipLaunchKernelGGL(k_h0_wave, dim3(L), dim3(64), 64 * 64 * 4 + 64 * 4 + 64 * 8, s4, dist, n, rowmax, a.thresh, stats,
-                               (uint32_t*)(B + p.o_mst), p.mst_words, (Pair*)(B + p.o_pairs[0]), p.pcap[0]);
-        } else {
-            int T = n <= 256 ? 256 : 1024;
-            if (n <= kH0WaveMaxN && !test_env_is("TDA_H0_WAVE", "0")) T = 1024;  // LDS Borůvka: a wave per vertex
-            // best | par | red | sort chunk | (LDS rows) | Borůvka hooks
-            size_t base = 16 + (size_t)n * 8 + (size_t)((n + 1) & ~1) * 4 + 40 * 8 + (size_t)n * 4;
-            base = align_up(base, 16);
-            // n <= kH0WaveMaxN: one-wave Prim on the LDS-staged matrix (sort chunk just covers the forest)
-            const bool wave_ok = !test_env_is("TDA_H0_WAVE", "0");
-            const bool dlds = n <= kH0WaveMaxN && wave_ok;
-            size_t avail = kLdsMax - base - (dlds ? (size_t)4 * n * n : 0);
-            uint64_t ch = 1;
-            if (dlds)
-                ch = next_pow2((uint64_t)n);
-            else
-                while (ch * 2 * 8 <= avail && ch * 2 <= 16384) ch *= 2;
-            size_t lds = base + ch * 8 + (dlds ? (size_t)4 * n * n : 0);
-            if (dlds) {
-                hipLaunchKernelGGL((k_h0<kH0WaveQ, true>), dim3(L), dim3(T), lds, s4, dist, n, a.thresh, stats, (uint32_t*)(B + p.o_mst),
-                                   p.mst_words, (Pair*)(B + p.o_pairs[0]), p.pcap[0], (uint64_t*)(B + p.o_h0s), ilog2(ch),
-                                   (const BorCtl*)nullptr);
-            } else {  // Borůvka over the whole GPU: ceil(log2 N) rounds of (cheapest edges, hooking)
-                int32_t* bcomp = (int32_t*)(B + p.o_bcomp);
-                uint64_t* bcheap = (uint64_t*)(B + p.o_bcheap);
-                BorCtl* bctl = (BorCtl*)(B + p.o_bctl);
-                hipLaunchKernelGGL(k_bor_init, dim3(L), dim3(256), 0, s4, rowmax, n, a.thresh, stats, bcomp, bcheap, bctl);
-                const size_t hl = (size_t)((n + 3) & ~3) * 8 + (size_t)n * 8;
-                const int rounds = std::max(1, ilog2(next_pow2((uint64_t)n)));
-                for (int r = 0; r < rounds; ++r) {
-                    hipLaunchKernelGGL(k_bor_min, dim3((unsigned)((n + 3) / 4), L), dim3(256), 0, s4, dist, n, stats, bcomp, bcheap, bctl,
-                                       r == 0 ? 1 : 0);
-                    if (r == 0)
-                        if (int rc = tm4.mark("k_bor_min")) return rc;
-                    hipLaunchKernelGGL(k_bor_hook, dim3(L), dim3(1024), hl, s4, n, bcomp, bcheap, bctl, (uint64_t*)(B + p.o_h0s));
-                    if (r == 0)
-                        if (int rc = tm4.mark("k_bor_hook")) return rc;
-                }
-                HIPC(hipGetLastError());
-                if (int rc = tm4.mark("k_bor_rounds")) return rc;
-                // elder rule: one wave with register labels up to N = 64 * kH0BorWQ, thread 0 above
-                if (n <= 64 * kH0BorWQ)
-                    hipLaunchKernelGGL((k_h0<kH0BorWQ, false, true>), dim3(L), dim3(T), lds, s4, dist, n, a.thresh, stats,
-                                       (uint32_t*)(B + p.o_mst), p.mst_words, (Pair*)(B + p.o_pairs[0]), p.pcap[0], (uint64_t*)(B + p.o_h0s),
-                                       ilog2(ch), (const BorCtl*)bctl);
-                else
-                    hipLaunchKernelGGL((k_h0<0, false, true>), dim3(L), dim3(T), lds, s4, dist, n, a.thresh, stats, (uint32_t*)(B + p.o_mst),
-                                       p.mst_words, (Pair*)(B + p.o_pairs[0]), p.pcap[0], (uint64_t*)(B + p.o_h0s), ilog2(ch),
-                                       (const BorCtl*)bctl);
-            }
-        }
-        HIPC(hipGetLastError());
-        if (!no_ph)
-            if (int rc = tm4.mark("k_h0")) return rc;
-        HIPC(hipEventRecord(w.evh, s4));
-        if (nls) {  // silhouette scores on the same distance matrices (sklearn semantics), after the H0 join
-            const size_t lds = (size_t)sil_K * kSilT * 8 + (size_t)n * 4;
-            hipLaunchKernelGGL(k_silhouette, dim3(L, nls), dim3(kSilT), lds, s4, dist, n, (const int32_t*)w.hsil_dev, sil_K,
-                               (double*)(w.hsil_dev + sil_out_off));
-            HIPC(hipGetLastError());
-            if (int rc = tm4.mark("k_silhouette")) return rc;
-        }
-        if (want_tn) {  // TwoNN intrinsic dimension on the same distance matrices
-            // beside H0 on the ranks stream when there are no ranks (the raw-activation sweeps:
-            // H0 and TwoNN only read the distances; r03 raw4096: they ran back to back on s4)
-            // (only without H1: with H1 the main stream joins s2 before the reduction, and
-            // TwoNN there would sit on the critical path -- ADVICE r03)
-            const bool tn_s2 = !p.dense && p.maxdim == 0;
-            const int pw2 = (int)next_pow2((uint64_t)std::max(n, 64));
-            hipLaunchKernelGGL(k_twonn, dim3(L), dim3(kTnT), (size_t)pw2 * 4, tn_s2 ? s2 : s4, dist, n, a.twonn_discard, a.twonn_eps, pw2,
-                               w.htn_dev);
-            HIPC(hipGetLastError());
-            if (int rc = (tn_s2 ? tm2 : tm4).mark("k_twonn")) return rc;
-        }
-        if (nls || want_tn) HIPC(hipEventRecord(w.evsil, s4));
-        if (p.dense) {  // triangle ranks for the dense H1 chain, off the critical path
-            dnb.recs = (EdgeRec*)(B + p.o_recs);
-            dnb.cls = (uint32_t*)(B + p.o_cls);
-            dnb.res1 = (uint32_t*)(B + p.o_res1);
-            dnb.inv32 = (uint32_t*)(B + p.o_inv32);
-            dnb.rank_of = (uint16_t*)(B + p.o_rof);
-            dnb.tri_stride = p.tri_stride;
-            dnb.cls2 = (uint16_t*)(B + p.o_cls2);
-            dnb.n2p = p.n2p;
-            dnb.inv = (uint16_t*)(B + p.o_inv);
-            dnb.E = (uint32_t)binom((uint64_t)n, 2);
-            dnb.inv_stride = p.inv_stride;
-            dnb.K = p.dK;
-            dnb.epos = (uint32_t*)(B + p.o_epos);
-            dnb.cobt = (uint16_t*)(B + p.o_cobt);
-            dnb.cob_stride = p.cob_stride;
-            dnb.eM = (uint64_t*)(B + p.o_eM);
-            dnb.necnt = (uint32_t*)(B + p.o_necnt);
-            const dim3 pg((unsigned)L, (unsigned)((dnb.E + kPrepEdges - 1) / kPrepEdges + 1));  // + the rank-sort block
-            hipLaunchKernelGGL(k_prep_edges, pg, dim3(kPrepT), p.prep_lds, s2, dist, n, rowmax, a.thresh, dnb, p.cmode, stats);
-            HIPC(hipGetLastError());
-            if (int rc = tm2.mark("k_prep_edges")) return rc;
-            // blocks per layer: 8 up to 64 layers (sweep48, 32 layers: 27 -> 18 us), 4 above (256 layers:
-            // 83 us with 4, 96 with 8 -- the per-block staging and scan then cost more than the spread saves)
-            const int ptb = test_env("TDA_PREP_TAB_BLOCKS") ? std::max(1, atoi(test_env("TDA_PREP_TAB_BLOCKS")))
-                                                           : (L <= 64 ? 2 * kPrepTabBlocks : kPrepTabBlocks);
-            hipLaunchKernelGGL(k_prep_tables, dim3(L, ptb), dim3(kPrepTabT), prep_tables_lds(n), s2, dist, n, dnb, p.cmode, stats);
-            HIPC(hipGetLastError());
-            if (int rc = tm2.mark("k_prep_tables")) return rc;
-        }
-        HIPC(hipEventRecord(w.evj, s2));
-        return 0;
-    };
-
-    // ---- H1 .. Hmaxdim: apparent pairs (parallel), residual sort, serial reduction
-    DimBufs db[3] = {};
-    for (int d = 1; d <= p.maxdim; ++d) {
-        db[d].cleared = d == 1 ? nullptr : (const uint32_t*)(B + p.o_piv[d - 1]);
-        db[d].cleared_words = d == 1 ? 0 : p.piv_words[d - 1];
-        db[d].pivbits = (uint32_t*)(B + p.o_piv[d]);
-        db[d].piv_words = p.piv_words[d];
-        db[d].resid = (uint64_t*)(B + p.o_resid[d]);
-        db[d].rcap = p.rcap[d];
-        db[d].ncand = p.ncand[d];
-        db[d].clr = d == 2 && p.piv2_sparse ? (uint64_t*)(B + p.o_clr2) : nullptr;
-        db[d].clr_cap = d == 2 && p.piv2_sparse ? p.clr_cap : 0;
-    }
-    // N <= 64 with H2: the H2 columns (apparent<2>, their sort, phase 1) run
-    // on a third stream beside the H1 chain; they only need apparent<1>'s
-    // pivot bitmap, and the chain records its residual pivots separately
-    const bool split2 = p.dense && p.maxdim >= 2;
-    auto launch_apparent = [&](int d, hipStream_t st, uint64_t total_override = 0) {
-        uint64_t blocks = (p.ncand[d] + 255) / 256;
-        // total blocks over all layers: measured (r01, sweep48) 1024 beats 4096,
-        // whose grid holds every CU while the critical small kernels wait; off
-        // the dense path the apparent kernels run alone: 4096 (r02, grid144:
-        // apparent<2> 1.08 -> 0.87 ms; staging the 83-KB matrix in LDS: 2.25 ms)
-        const char* app_env = test_env("TDA_APP_GRID");
-        const uint64_t app_total = app_env ? strtoull(app_env, nullptr, 10) : total_override ? total_override : (p.dense ? 1024 : 4096);
-        unsigned gx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(blocks, std::max<uint64_t>(1, app_total / L)));
-        const int app_lds_max = test_env("TDA_APP_LDS_MAXN") ? atoi(test_env("TDA_APP_LDS_MAXN")) : kAppLdsMaxN;
-        const bool dl = n <= app_lds_max && 16 + (size_t)n * n * 4 <= (size_t)kLdsMax;
-        const size_t alds = 16 + (dl ? (size_t)n * n * 4 : 0);
-        // N <= 64: the small-N pass (32-bit decode, 4 vertices per LDS read); TDA_APP_SMALL=0 -> k_apparent
-        if (n <= 64 && dl && !test_env_is("TDA_APP_SMALL", "0")) {
-            // the pivot bitmap copied in LDS when it fits and a block's simplices outnumber a quarter
-            // of its words (every block flushes the whole copy): r06, 160 layers per call,
-            // apparent<1> 24.7 -> 19.3 us, apparent<2> 73.7 -> 57.0 us; at 32 layers per call (540
-            // triangles per block) the flushes cost more than the atomics saved: call 0.171 -> 0.177 ms.
-            // TDA_APP_PIV_LDS=0 / 1: never / always.
-            const uint64_t per_block = (p.ncand[d] + gx - 1) / gx;
-            const bool pl_fit = db[d].piv_words * 4 <= kSmallPivLdsMax;
-            const bool pl_on = test_env_is("TDA_APP_PIV_LDS", "1") ? pl_fit
-                               : test_env_is("TDA_APP_PIV_LDS", "0") ? false
-                                                                    : pl_fit && per_block * 4 >= db[d].piv_words;
-            const uint32_t pl_words = pl_on ? (uint32_t)db[d].piv_words : 0u;
-            const size_t slds = 16 + small_piv_offset(n) + 4ull * pl_words;
-            if (d == 1)
-                hipLaunchKernelGGL((k_apparent_small<1>), dim3(gx, L), dim3(256), slds, st, dist, n, stats, db[d], rowmax, a.thresh, pl_words);
-            else
-                hipLaunchKernelGGL((k_apparent_small<2>), dim3(gx, L), dim3(256), slds, st, dist, n, stats, db[d], rowmax, a.thresh, pl_words);
-        } else {
-            // L a multiple of 8: a 1-D grid whose blocks take their layers XCD by XCD (app_block)
-            const int xl = (L % 8 == 0 && !test_env_is("TDA_APP_XCD", "0")) ? L : 0;
-            const dim3 ag = xl ? dim3(gx * (unsigned)L) : dim3(gx, L);
-            // H1 above the LDS-matrix range: 16 x 16 edge tiles over LDS-staged v-tiles (TDA_APP_TILE=0: one edge per thread)
-            const bool tiled = d == 1 && !dl && !test_env_is("TDA_APP_TILE", "0");
-            if (tiled) {
-                const uint64_t nt = ((uint64_t)n + kAppTS - 1) / kAppTS, tiles = nt * (nt + 1) / 2;
-                const unsigned tx = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(tiles, std::max<uint64_t>(1, app_total / L)));
-                const dim3 tg = xl ? dim3(tx * (unsigned)L) : dim3(tx, L);
-                hipLaunchKernelGGL(k_apparent_tile, tg, dim3(256), 0, st, dist, n, stats, db[d], rowmax, a.thresh, xl);
-            } else if (d == 1 && dl)
-                hipLaunchKernelGGL((k_apparent<1, true>), ag, dim3(256), alds, st, dist, n, stats, db[d], rowmax, a.thresh, xl);
-            else if (d == 1)
-                hipLaunchKernelGGL((k_apparent<1, false>), ag, dim3(256), alds, st, dist, n, stats, db[d], rowmax, a.thresh, xl);
-            else if (dl)
-                hipLaunchKernelGGL((k_apparent<2, true>), ag, dim3(256), alds, st, dist, n, stats, db[d], rowmax, a.thresh, xl);
-            else
-                hipLaunchKernelGGL((k_apparent<2, false>), ag, dim3(256), alds, st, dist, n, stats, db[d], rowmax, a.thresh, xl);
-        }
-    };
-    Reduce2Bufs rb;
-    rb.rmap_keys = (uint64_t*)(B + p.o_rmk);
-    rb.rmap_vals = (uint32_t*)(B + p.o_rmv);
-    rb.rmap_stride = p.rmap_stride;
-    rb.roff = (uint64_t*)(B + p.o_voff);
-    rb.rlen = (uint32_t*)(B + p.o_vlen);
-    rb.rpool = (uint64_t*)(B + p.o_vpool);
-    rb.rpool_cap = p.vpool_cap;
-    rb.wtmp = (uint64_t*)(B + p.o_wt);
-    rb.wtmp_stride = 2 * (p.lds_mode ? 8192 : p.wcap_g);
-    rb.wlog = (uint64_t*)(B + p.o_wk);
-    rb.windex = (uint64_t*)(B + p.o_wl);
-    rb.wfill = (uint32_t*)(B + p.o_wp);
-    rb.wcap = p.wcap_g;
-    rb.mst = (const uint32_t*)(B + p.o_mst);
-    rb.mst_words = p.mst_words;
-    SortArgs sa = {};
-    for (int d = 1; d <= p.maxdim; ++d) {
-        sa.resid[d] = db[d].resid;
-        sa.rcap[d] = db[d].rcap;
-    }
-    auto launch_sort = [&](int d0, int nd, hipStream_t st, uint64_t max_chunk = 16384) {
-        // LDS chunk: the largest residual list of these dims, at most max_chunk keys
-        uint64_t cap = 64;
-        for (int d = d0; d < d0 + nd; ++d) cap = std::max<uint64_t>(cap, std::min<uint64_t>(next_pow2(p.rcap[d]), max_chunk));
-        hipLaunchKernelGGL(k_sort_resid, dim3(L, nd), dim3(1024), cap * 8, st, stats, sa, (uint64_t*)(B + p.o_tmp), p.max_rcap,
-                           rb.rmap_keys, rb.rmap_stride, ilog2(cap), d0);
-    };
-    SmallBufs sb = {};
-    if (p.dense) {
-        sb.p1_next = (uint32_t*)(B + p.o_p1next);
-        sb.p1_key = (uint64_t*)(B + p.o_p1k);
-        sb.p1_info = (uint32_t*)(B + p.o_p1i);
-        sb.p1_pidx = (uint32_t*)(B + p.o_p1x);
-        sb.roff2 = (uint64_t*)(B + p.o_roff2);
-        sb.rlen2 = (uint32_t*)(B + p.o_rlen2);
-        sb.rpool2 = (uint64_t*)(B + p.o_rpool2);
-        sb.rpool2_cap = p.vpool_cap;
-        sb.p1_used = (unsigned long long*)(B + p.o_p1used);
-        sb.p1_wcap = kP1WCap;
-    }
-    // H2 phase 1 (its early exits read the chain's residual H1 pivots as they
-    // appear); in the one-stream timing mode it runs right after the chain,
-    // so it sees what it sees when it runs beside it
-    auto launch_phase1 = [&](hipStream_t st) -> int {
-        // blocks per layer: each holds ~46 KB of LDS (one wave), so the whole grid is occupancy-bound:
-        // ~1 K blocks over all layers (r04, sweep48 serial stage: L = 32: 96 -> 32 blocks 35 -> 28 us;
-        // L = 128: 96 -> 16 blocks 108 -> 73 us); small batches keep up to kP1Grid
-        const int p1g = test_env("TDA_P1_GRID") ? std::max(1, atoi(test_env("TDA_P1_GRID")))
-                                                : std::min(kP1Grid, std::max(16, 1024 / std::max(1, L)));
-        hipLaunchKernelGGL(k_h2_phase1, dim3(L, (p1g + p.p1_waves - 1) / p.p1_waves), dim3(64 * p.p1_waves), p.p1_lds, st, dist, n, stats, db[2], sb, (const uint16_t*)dnb.cls2,
-                           p.n2p, p.bm_words, (const uint32_t*)dnb.res1, (uint32_t)p.piv_words[1], step_limit());
-        HIPC(hipGetLastError());
-        if (int rc = (st == s ? tm : tm3).mark("k_h2_phase1")) return rc;
-        HIPC(hipEventRecord(w.evp, st));
-        return 0;
-    };
-    // capture order of the launches (the graph executor dispatches in it):
-    // TDA_ORDER=0 apparent<1> first; 1 side streams first; 2 side streams
-    // first and the H2 branch after the triangle ranks; 3 side streams first,
-    // sort<1> enqueued before the H2 branch; 5 (N <= 64 with H2) as 3, with
-    // apparent<1> at the head of the H2 branch's stream: sweep48 0.182 ->
-    // 0.175 ms device, L = 4 0.136 -> 0.131 ms (replayed graph; eager slower)
-    // 5 up to 64 layers per call; 3 above (sweep48x4, 128 layers: 0.42 vs 0.48 ms with 5)
-    // r04 (after the §6.4-6.5 kernel changes, graph replay, one call at a time): L = 32 order 2 0.167 ms
-    // device vs 0.174 with 5; L = 4 order 5 0.124 ms vs 0.138 with 2
-    const int order = test_env("TDA_ORDER") ? atoi(test_env("TDA_ORDER")) : (L <= 16 ? 5 : L <= 64 ? 2 : 3);
-    if (p.maxdim < 1 || order >= 1)
-        if (int rc = launch_side()) return rc;
-    const bool h2_side = !p.dense && p.par && p.par2 && p.maxdim >= 2;
-    // the H2 branch forks once k_reduce_par<1> is about to start (after k_par_init), not after
-    // apparent<1>: launched together with the H1 prerequisites, the GPU-filling apparent<2> pass
-    // slowed them (torus2048_h2 trace: sort<1> 0.06 -> 7 ms, the edge chunk sort 0.5 -> 15 ms, the
-    // H1 reduction starting at 26.6 ms); after k_par_init it fills the CUs the H1 workers leave.
-    // The wide edge codes (H2 keys only) move onto the branch too.  TDA_H2_LATE=0: the r04 fork.
-    const bool h2_late = h2_side && !test_env_is("TDA_H2_LATE", "0");
-    // A k_reduce_par worker fills a CU (two 256-VGPR waves per SIMD), so apparent<2> blocks
-    // dispatched before the H1 workers keep them off every CU they hold (torus2048_h2: the H1
-    // reduction 124 -> 154 ms); on a small grid the pass itself crawls (128 blocks: 30 -> 194 ms).
-    // The branch starts after a short device-side delay instead, so the H1 workers are resident
-    // first and apparent<2> fills the CUs they leave as the column queue drains.
-    const uint64_t h2_late_grid = test_env("TDA_H2_LATE_GRID") ? strtoull(test_env("TDA_H2_LATE_GRID"), nullptr, 10) : 0;
-    const uint32_t h2_late_delay_us = test_env("TDA_H2_LATE_DELAY") ? (uint32_t)atoi(test_env("TDA_H2_LATE_DELAY")) : 50;
-    auto launch_h2_columns = [&]() -> int {  // apparent<2> + their sort on the third stream
-        if (int rc = tm3.begin()) return rc;
-        launch_apparent(2, w.stream3, h2_late ? h2_late_grid : 0);
-        HIPC(hipGetLastError());
-        if (int rc = tm3.mark("k_apparent<2>")) return rc;
-        // beside k_reduce_par<1> (one 72-KB workgroup per CU) the sort's LDS chunk must fit next to
-        // it: 4096 keys (32 KB); a 128-KB chunk waited for the H1 reduction (grid144: 0.85 ms)
-        launch_sort(2, 1, w.stream3, h2_side ? 4096 : 16384);
-        HIPC(hipGetLastError());
-        if (int rc = tm3.mark("k_sort_resid<2>")) return rc;
-        return 0;
-    };
-    Pair* const pairs1 = (Pair*)(B + p.o_pairs[1]);
-    Pair* const pairs2 = p.maxdim >= 2 ? (Pair*)(B + p.o_pairs[2]) : pairs1;
-    auto launch_chain = [&](hipStream_t st) -> int {  // dense H1 (N <= 64): one k_h1_chain instantiation per (words, mode)
-        switch (p.dK * 3 + p.cmode) {
-#define TDA_CHAIN(K, F)                                                                                                          \
-    case K * 3 + F:                                                                                                              \
-        hipLaunchKernelGGL((k_h1_chain<K, F>), dim3(L), dim3(kChainT), p.chain_lds, st, dist, n, stats, db[1], rb, dnb, step_limit(), \
-                           pairs1, p.pcap[1]);                                                                                   \
-        break;
-            TDA_CHAIN(1, 0) TDA_CHAIN(2, 0) TDA_CHAIN(3, 0) TDA_CHAIN(4, 0) TDA_CHAIN(6, 0) TDA_CHAIN(9, 0) TDA_CHAIN(12, 0)
-            TDA_CHAIN(16, 0) TDA_CHAIN(21, 0)
-            TDA_CHAIN(1, 1) TDA_CHAIN(2, 1) TDA_CHAIN(3, 1) TDA_CHAIN(4, 1) TDA_CHAIN(6, 1) TDA_CHAIN(9, 1) TDA_CHAIN(12, 1)
-            TDA_CHAIN(1, 2) TDA_CHAIN(2, 2) TDA_CHAIN(3, 2) TDA_CHAIN(4, 2) TDA_CHAIN(6, 2) TDA_CHAIN(9, 2) TDA_CHAIN(12, 2)
-#undef TDA_CHAIN
-            default:
-                return fail(TDA_E_INVALID, "no k_h1_chain instantiation for this N");
-        }
-        HIPC(hipGetLastError());
-        return 0;
-    };
-    auto launch_h2_finish = [&](hipStream_t st) -> int {
-        hipLaunchKernelGGL(k_reduce_h2_finish, dim3(L), dim3(64), p.rcfg.bytes, st, dist, n, stats, db[1], db[2], rb, p.rcfg, sb,
-                           (const uint32_t*)dnb.res1, pairs2, p.pcap[2]);
-        HIPC(hipGetLastError());
-        return 0;
-    };
-    // order 5 (N <= 64, H0-H2): apparent<1> opens the H2 branch's stream (its pivot
-    // bitmap is apparent<2>'s clearing test), so the branch runs on one queue up to
-    // phase 1; the main stream picks up apparent<1>'s residuals for sort<1> and the chain
-    const bool app1_side = split2 && order == 5 && !serial_stages;
-    if (p.maxdim >= 1 && app1_side) {
-        HIPC(hipStreamWaitEvent(w.stream3, w.evf, 0));
-        if (int rc = tm3.begin()) return rc;
-        launch_apparent(1, w.stream3);
-        HIPC(hipGetLastError());
-        if (int rc = tm3.mark("k_apparent<1>")) return rc;
-        HIPC(hipEventRecord(w.evs, w.stream3));
-        launch_apparent(2, w.stream3);
-        HIPC(hipGetLastError());
-        if (int rc = tm3.mark("k_apparent<2>")) return rc;
-        launch_sort(2, 1, w.stream3, 16384);
-        HIPC(hipGetLastError());
-        if (int rc = tm3.mark("k_sort_resid<2>")) return rc;
-        HIPC(hipStreamWaitEvent(w.stream3, w.evj, 0));  // edge classes (k_prep_*)
-        if (int rc = launch_phase1(w.stream3)) return rc;
-        HIPC(hipStreamWaitEvent(s, w.evs, 0));
-        launch_sort(1, 1, s);
-        HIPC(hipGetLastError());
-        MARK("k_sort_resid<1>");
-    }
-    if (p.maxdim >= 1) {
-        if (!app1_side) {
-            launch_apparent(1, s);
-            HIPC(hipGetLastError());
-            MARK("k_apparent<1>");
-        }
-        if (order == 0)
-            if (int rc = launch_side()) return rc;
-        if (app1_side) {
-            // enqueued above
-        } else if (split2) {
-            HIPC(hipEventRecord(w.evs, s));
-            if (order == 3) {
-                launch_sort(1, 1, s);
-                HIPC(hipGetLastError());
-                MARK("k_sort_resid<1>");
-            }
-            HIPC(hipStreamWaitEvent(w.stream3, w.evs, 0));
-            if (order == 2) HIPC(hipStreamWaitEvent(w.stream3, w.evj, 0));
-            if (int rc = launch_h2_columns()) return rc;
-            HIPC(hipStreamWaitEvent(w.stream3, w.evj, 0));  // edge classes (k_prep_*)
-            if (!serial_stages)
-                if (int rc = launch_phase1(w.stream3)) return rc;
-            if (order != 3) {
-                launch_sort(1, 1, s);
-                HIPC(hipGetLastError());
-                MARK("k_sort_resid<1>");
-            }
-        } else if (h2_side && h2_late) {
-            // (fork after k_par_init below)
-            launch_sort(1, 1, s);
-            HIPC(hipGetLastError());
-            MARK("k_sort_resid<1>");
-        } else if (h2_side) {
-            // parallel H1 and H2: the H2 columns' apparent pass and sort run on
-            // the third stream beside the H1 reduction (k_reduce_par<2> joins
-            // them).  k_par_emit<1> may OR residual H1 pivots into the bitmap
-            // k_apparent<2> reads as its clearing test while it runs: a triangle
-            // seen cleared is skipped there, otherwise it becomes a residual
-            // column that k_reduce_par<2> skips -- never an apparent pair (a
-            // cleared triangle is an H1 death, and apparent pairs are
-            // persistence pairs), so pairs and checksums do not depend on the race.
-            HIPC(hipEventRecord(w.evs, s));
-            HIPC(hipStreamWaitEvent(w.stream3, w.evs, 0));
-            if (int rc = launch_h2_columns()) return rc;
-            HIPC(hipEventRecord(w.evp, w.stream3));
-            launch_sort(1, 1, s);
-            HIPC(hipGetLastError());
-            MARK("k_sort_resid<1>");
-        } else {
-            for (int d = 2; d <= p.maxdim; ++d) {
-                launch_apparent(d, s);
-                HIPC(hipGetLastError());
-                MARK("k_apparent<2>");
-            }
-            launch_sort(1, p.maxdim, s);
-            HIPC(hipGetLastError());
-            MARK("k_sort_resid");
-        }
-        if (p.serial_tables) {
-            HIPC(hipMemsetAsync(rb.windex, 0, (size_t)L * p.wcap_g * 2 * 8, s));
-            HIPC(hipMemsetAsync(rb.wfill, 0, (size_t)L * p.wcap_g / 4 * 4, s));
-        }
-        HIPC(hipStreamWaitEvent(s, w.evh, 0));  // join: forest edges (clearing of H1 columns)
-        HIPC(hipStreamWaitEvent(s, w.evj, 0));  // join: triangle ranks
-        MARK("wait:join");  // keeps the side streams' time out of the next kernel's stage
-        const bool p1 = n <= 1024, p2 = n <= 256;
-        const ReduceAllCfg& rc = p.rcfg;
-#define TDA_LAUNCH_RED(LW, P1, P2)                                                                                        \
-    hipLaunchKernelGGL((k_reduce_all<LW, P1, P2>), dim3(L), dim3(64), rc.bytes, s, dist, n, p.maxdim, stats, db[1], db[2], rb, rc, \
-                       pairs1, pairs2, p.pcap[1], p.maxdim >= 2 ? p.pcap[2] : 0)
-        if (p.dense) {
-            if (int rc = launch_chain(s)) return rc;
-            MARK("k_h1_chain");
-            if (p.maxdim >= 2) {
-                if (serial_stages)
-                    if (int rc = launch_phase1(s)) return rc;
-                HIPC(hipStreamWaitEvent(s, w.evp, 0));  // phase-1 results
-                MARK("wait:phase1");
-                if (int rc = launch_h2_finish(s)) return rc;
-                MARK("k_reduce_h2_finish");
-            }
-        } else if (p.big) {
-            BigBufs gb;
-            gb.log = rb.wlog;
-            gb.index = rb.windex;
-            gb.fill = rb.wfill;
-            gb.bref = (uint32_t*)(B + p.o_bref);
-            gb.cap = p.wcap_g;
-            gb.bcap = p.wcap_g;
-            gb.step_limit = step_limit();
-            gb.wide = p.wide ? 1 : 0;
-            gb.dcode = (const uint32_t*)(B + p.o_dcode);
-            gb.dsort = (const uint64_t*)(B + p.o_dsort);
-            gb.ecap = p.ecap;
-            // edge codes of the wide H2 keys (thresholds are known: after the H0 join)
-            auto launch_edge_codes = [&](hipStream_t es, StageTimer& et) -> int {
-                // the sorted lengths end in dsort: with an odd number of merge passes the keys start in dtmp
-                const uint64_t E = binom((uint64_t)n, 2), CH = 1ull << kEdgeSortLog2;
-                int passes = 0;
-                for (uint64_t w = CH; w < E; w <<= 1) ++passes;
-                uint64_t* ka = (uint64_t*)(B + ((passes & 1) ? p.o_dtmp : p.o_dsort));
-                uint64_t* kb = (uint64_t*)(B + ((passes & 1) ? p.o_dsort : p.o_dtmp));
-                const unsigned gk = (unsigned)std::min<uint64_t>(1024, ((uint64_t)n * n + 255) / 256);
-                hipLaunchKernelGGL(k_edge_keys, dim3(gk, L), dim3(256), 0, es, dist, n, ka, p.ecap);
-                hipLaunchKernelGGL(k_edge_chunks, dim3((unsigned)((E + CH - 1) / CH), L), dim3(1024), kEdgeSortLds, es, ka, E, p.ecap);
-                for (uint64_t w = CH; w < E; w <<= 1) {
-                    hipLaunchKernelGGL(k_edge_merge, dim3((unsigned)((E + kMergeSeg - 1) / kMergeSeg), L), dim3(256), 0, es, ka, kb, E,
-                                       p.ecap, w);
-                    std::swap(ka, kb);
-                }
-                HIPC(hipGetLastError());
-                if (int rc = et.mark("k_edge_sort")) return rc;
-                const unsigned gx = (unsigned)std::min<uint64_t>(1024, ((uint64_t)n * n + 255) / 256);
-                hipLaunchKernelGGL(k_edge_codes, dim3(gx, L), dim3(256), 0, es, dist, n, stats, (const uint64_t*)(B + p.o_dsort), p.ecap,
-                                   (uint32_t*)(B + p.o_dcode));
-                HIPC(hipGetLastError());
-                return et.mark("k_edge_codes");
-            };
-            if (p.wide && !h2_late)
-                if (int rc = launch_edge_codes(s, tm)) return rc;
-            int start_dim = 1;
-            if (p.par) {
-                ParBufs pb;
-                pb.ctl = (ParCtl*)(B + p.o_pctl);
-                pb.item_base = (uint64_t*)(B + p.o_pitem);
-                pb.okey = (uint64_t*)(B + p.o_pokey);
-                pb.oval = (uint64_t*)(B + p.o_poval);
-                pb.ostride = p.ostride;
-                pb.colpiv = (uint64_t*)(B + p.o_colpiv);
-                pb.rec = (uint64_t*)(B + p.o_prec);
-                pb.rec_cap = p.rec_cap;
-                pb.rpool = (uint64_t*)(B + p.o_prpool);
-                pb.rpool_cap = p.rpool_cap;
-                pb.bpool = (uint64_t*)(B + p.o_pbpool);
-                pb.bpool_cap = p.bpool_cap;
-                pb.rq = (uint64_t*)(B + p.o_prq);
-                pb.rq_cap = p.rq_cap;
-                pb.step_limit = step_limit();
-                pb.capf = capf;
-                pb.dbg = p.o_pdbg ? (uint64_t*)(B + p.o_pdbg) : nullptr;  // profile builds only
-                HIPC(hipMemsetAsync(pb.rq, 0, p.rq_cap * 8, s));
-                hipLaunchKernelGGL(k_par_init, dim3(64, L), dim3(256), 0, s, stats, L, p.rcap[1], pb, 1);
-                HIPC(hipGetLastError());
-                MARK("k_par_init");
-                if (h2_late) {  // the H2 branch (and the wide edge codes) beside the H1 reduction
-                    HIPC(hipEventRecord(w.evs, s));
-                    HIPC(hipStreamWaitEvent(w.stream3, w.evs, 0));
-                    if (h2_late_delay_us && !serial_stages)
-                        hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, w.stream3, h2_late_delay_us);
-                    if (int rc = launch_h2_columns()) return rc;
-                    if (p.wide)
-                        if (int rc = launch_edge_codes(w.stream3, tm3)) return rc;
-                    HIPC(hipEventRecord(w.evp, w.stream3));
-                }
-                // persistent workers (one 71-KB-LDS workgroup per CU by default); the surplus exits at once
-                const unsigned par_grid = par_grid_size();
-                const uint32_t* no_clr = nullptr;
-                if (p.packed)
-                    hipLaunchKernelGGL((k_reduce_par<1, true>), dim3(par_grid), dim3(kParT), sizeof(ParLds), s, dist, n, L, stats, db[1], no_clr,
-                                       (uint64_t)0, rb, pb, gb.dcode, gb.dsort, gb.ecap);
-                else
-                    hipLaunchKernelGGL((k_reduce_par<1, false>), dim3(par_grid), dim3(kParT), sizeof(ParLds), s, dist, n, L, stats, db[1], no_clr,
-                                       (uint64_t)0, rb, pb, gb.dcode, gb.dsort, gb.ecap);
-                HIPC(hipGetLastError());
-                MARK("k_reduce_par");
-                // H2 next: residual H1 pivots into the dim-1 bitmap (k_reduce_par<2>) or map (k_reduce_big)
-                hipLaunchKernelGGL(k_par_emit<1>, dim3(L), dim3(1024), 0, s, stats, db[1], rb, pb, pairs1, p.pcap[1],
-                                   p.maxdim < 2 ? 0 : p.par2 ? 2 : 1, (const uint64_t*)nullptr, (uint64_t)0);
-                HIPC(hipGetLastError());
-                MARK("k_par_emit");
-                start_dim = 2;
-                if (p.par2) {  // H2 columns on the same workers (an H1 abort skips it: k_par_init keeps the flag)
-                    if (h2_side) HIPC(hipStreamWaitEvent(s, w.evp, 0));  // join: H2 columns (third stream)
-                    HIPC(hipMemsetAsync(pb.rq, 0, p.rq_cap * 8, s));
-                    hipLaunchKernelGGL(k_par_init, dim3(64, L), dim3(256), 0, s, stats, L, p.rcap[2], pb, 2);
-                    HIPC(hipGetLastError());
-                    if (p.wide)  // N > 568: edge-code keys (k_edge_codes ran above)
-                        hipLaunchKernelGGL((k_reduce_par<2, false, true>), dim3(par_grid), dim3(kParT), sizeof(ParLds), s, dist, n, L, stats,
-                                           db[2], (const uint32_t*)db[1].pivbits, db[1].piv_words, rb, pb, gb.dcode, gb.dsort, gb.ecap);
-                    else if (n <= kPar2PackedMaxN)
-                        hipLaunchKernelGGL((k_reduce_par<2, true>), dim3(par_grid), dim3(kParT), sizeof(ParLds), s, dist, n, L, stats, db[2],
-                                           (const uint32_t*)db[1].pivbits, db[1].piv_words, rb, pb, gb.dcode, gb.dsort, gb.ecap);
-                    else
-                        hipLaunchKernelGGL((k_reduce_par<2, false>), dim3(par_grid), dim3(kParT), sizeof(ParLds), s, dist, n, L, stats, db[2],
-                                           (const uint32_t*)db[1].pivbits, db[1].piv_words, rb, pb, gb.dcode, gb.dsort, gb.ecap);
-                    HIPC(hipGetLastError());
-                    MARK("k_reduce_par<2>");
-                    hipLaunchKernelGGL(k_par_emit<2>, dim3(L), dim3(1024), 0, s, stats, db[2], rb, pb, pairs2, p.pcap[2], 0,
-                                       p.wide ? gb.dsort : (const uint64_t*)nullptr, p.ecap);
-                    HIPC(hipGetLastError());
-                    MARK("k_par_emit<2>");
-                    start_dim = 3;
-                }
-            }
-            if (start_dim <= p.maxdim)
-                hipLaunchKernelGGL(k_reduce_big, dim3(L), dim3(kBigT), 0, s, dist, n, p.maxdim, stats, db[1], db[2], rb, gb, pairs1,
-                                   pairs2, p.pcap[1], p.maxdim >= 2 ? p.pcap[2] : 0, start_dim);
-        } else if (p.lds_mode) {
-            if (p2) TDA_LAUNCH_RED(true, true, true); else if (p1) TDA_LAUNCH_RED(true, true, false); else TDA_LAUNCH_RED(true, false, false);
-        } else {
-            if (p2) TDA_LAUNCH_RED(false, true, true); else if (p1) TDA_LAUNCH_RED(false, true, false); else TDA_LAUNCH_RED(false, false, false);
-        }
-#undef TDA_LAUNCH_RED
-        HIPC(hipGetLastError());
-        if (!p.dense && !(p.par && (p.maxdim < 2 || p.par2))) MARK(p.big ? "k_reduce_big" : "k_reduce_all");
-    } else {
-        HIPC(hipStreamWaitEvent(s, w.evh, 0));
-        HIPC(hipStreamWaitEvent(s, w.evj, 0));
-    }
-
-    if (nls || want_tn) HIPC(hipStreamWaitEvent(s, w.evsil, 0));  // join: silhouette scores, TwoNN on s4
-    if (want_tn) HIPC(hipStreamWaitEvent(s, w.evj, 0));          // join: TwoNN on s2
-    // ---- emission order, straight into host-mapped memory
-    hipLaunchKernelGGL(k_emit, dim3(L), dim3(1024), kEmitLds, s, stats, L, p.maxdim, ps, (uint64_t*)(B + p.o_fk),
-                       (uint32_t*)(B + p.o_fv), p.sstride, w.houtoff_dev, w.hout_dev, (uint64_t)w.hout_cap, w.hstats_dev);
-    HIPC(hipGetLastError());
-    MARK("k_emit");
-    if (p.piv2_sparse) {  // the H2 pivot bitmap back to zero: only the words this call set
-        hipLaunchKernelGGL(k_clear_words, dim3(1024, L), dim3(256), 0, s, stats, (const uint64_t*)(B + p.o_clr2), p.clr_cap,
-                           (uint32_t*)(B + p.o_piv[2]), p.piv_words[2]);
-        HIPC(hipGetLastError());
-        MARK("k_clear_words");
-    }
-    HIPC(rec_t(w.ev1));
-    return 0;
-    };  // enqueue
-    // TDA_HOST_PROF=1: host-side time of the call's parts (stderr, every 200 calls)
-    static const bool host_prof = getenv_is("TDA_HOST_PROF", "1");
-    using hclk = std::chrono::steady_clock;
-    const auto h0 = hclk::now();
-    if (p.piv2_sparse) {  // first use of the region, or the last call left it dirty: one full memset
-        char* pv2 = B + p.o_piv[2];
-        const size_t bytes = (size_t)L * p.piv_words[2] * 4;
-        if (w.piv2_dirty || w.piv2_ptr != pv2 || w.piv2_bytes < bytes) {
-            HIPC(hipMemsetAsync(pv2, 0, bytes, s));
-            w.piv2_ptr = pv2;
-            w.piv2_bytes = bytes;
-        }
-        w.piv2_dirty = true;  // until this call has cleared the words it set
-    }
+    c.capture = use_graph && !ge;
     if (ge) {
         std::shared_lock<std::shared_mutex> launch_lock(g_launch_mu);
         HIPC(hipEventRecord(w.ev0, s));
         HIPC(hipGraphLaunch(ge->exec, s));
         HIPC(hipEventRecord(w.ev1, s));
-    } else if (capture) {
+    } else if (c.capture) {
         // capture + instantiate one graph at a time across the process: concurrent
         // captures from several slot threads crashed the HIP runtime once (r03, host
         // segfault inside a first call of two slots); replays run concurrently with each
@@ -1885,7 +1220,7 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
         std::lock_guard<std::mutex> cap_lock(g_capture_mu);
         std::unique_lock<std::shared_mutex> launch_lock(g_launch_mu);
         HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue();
+        const int rc = enqueue_schedule(c);
         hipGraph_t graph = nullptr;
         const hipError_t ce = hipStreamEndCapture(s, &graph);
         if (rc) {
@@ -1911,19 +1246,18 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
         HIPC(hipEventRecord(w.ev1, s));
     } else {
         std::shared_lock<std::shared_mutex> launch_lock(g_launch_mu);
-        if (int rc = enqueue()) return rc;
+        if (int rc = enqueue_schedule(c)) return rc;
     }
-    if (a.want_dist) {
-        HIPC(hipMemcpyAsync(w.hdist, dist, sizeof(float) * L * n * n, hipMemcpyDeviceToHost, s));
-        if (p.want64) HIPC(hipMemcpyAsync(w.hdist + sizeof(float) * L * n * n, B + p.o_d64, sizeof(double) * L * n * n, hipMemcpyDeviceToHost, s));
-    }
-    const auto h1 = hclk::now();
-    // (an event sync or a busy-polled end event measured the same for one call at a time, r02; and
-    // for six pipelined slots, hipStreamQuery polled in a loop: 697-701 vs 540-727 K layers/s, r06)
-    HIPC(hipStreamSynchronize(s));
-    const auto h2 = hclk::now();
+    return 0;
+}
 
-    int errs = 0;
+// After the call's synchronisation: the layers' error flags OR-ed (without ERR_CAP_MISS).  An
+// output overflow alone (ERR_OUT_CAP) is mended here: the pair buffer grows and k_emit runs again.
+int collect_errors(Call& c, int& errs) {
+    const Plan& p = c.p;
+    Workspace& w = c.w;
+    const int L = c.L;
+    errs = 0;
     for (int l = 0; l < L; ++l) errs |= w.hstats[l].err & ~ERR_CAP_MISS;
     if (p.piv2_sparse) {  // clean again unless a layer's word list overflowed
         bool over = false;
@@ -1942,216 +1276,65 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
             if (int rc = grow_hout(w, need + 16)) return rc;
         }
         for (int l = 0; l < L; ++l) w.hstats[l].err = 0;
-        HIPC(hipMemcpyAsync(stats, w.hstats, sizeof(LayerStats) * L, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_emit, dim3(L), dim3(1024), kEmitLds, s, stats, L, p.maxdim, ps, (uint64_t*)(B + p.o_fk),
-                           (uint32_t*)(B + p.o_fv), p.sstride, w.houtoff_dev, w.hout_dev, (uint64_t)w.hout_cap, w.hstats_dev);
+        HIPC(hipMemcpyAsync(c.stats, w.hstats, sizeof(LayerStats) * L, hipMemcpyHostToDevice, c.s));
+        launch_k_emit(c);
         HIPC(hipGetLastError());
-        HIPC(hipStreamSynchronize(s));
+        HIPC(hipStreamSynchronize(c.s));
         errs = 0;
         for (int l = 0; l < L; ++l) errs |= w.hstats[l].err & ~ERR_CAP_MISS;
     }
-    if (errs && getenv("TDA_DEBUG"))
-        fprintf(stderr, "[tda] N=%d L=%d errs=%s force_global=%d scale=%d\n", n, L, err_flags(errs).c_str(), (int)force_global, scale);
+    return 0;
+}
+
+// what follows from the call's error flags (next_attempt, rips_retry.h); a failure sets the message
+int decide_retry(Call& c, int errs, RetryStep& step) {
+    step = {RetryStep::kDone, c.at};
+    if (!errs) return 0;
+    ParCtl ctl = {};
     if (errs & (ERR_PAR | ERR_PAR2)) {
-        // k_reduce_par gave up (a capacity or spin limit): the whole call is re-run (distances,
-        // H0, apparent pairs included) with the reduction on the serial radix-heap kernel -- both
-        // dimensions after an H1 abort (ERR_PAR); after an H2 abort alone (ERR_PAR2) H1 stays on
-        // k_reduce_par and only H2 moves to k_reduce_big.  An abort costs the first call of a
-        // shape about twice its time; the retry memo skips the failing attempt on later calls.
-        const int np_next = (errs & ERR_PAR) ? 2 : std::max(no_par, 1);
-        ParCtl c;
-        HIPC(hipMemcpy(&c, B + p.o_pctl, sizeof(c), hipMemcpyDeviceToHost));
+        HIPC(hipMemcpy(&ctl, c.B + c.p.o_pctl, sizeof(ctl), hipMemcpyDeviceToHost));
         if (getenv("TDA_DEBUG"))
-            fprintf(stderr, "[tda] k_reduce_par aborted: code %llu, evictions %llu, records %llu, pools %llu / %llu keys\n", c.err,
-                    c.evictions, c.rec_used, c.rpool_used, c.bpool_used);
-        const unsigned code = (unsigned)(c.err & 0xFFFF);
-        const bool capacity = code == 21 || code == 22 || code == 41 || code == 53;  // pools / requeue slots
-        // (a noisy circle at N = 1024 needs ~450 M bucket keys for its one long column, 4x the
-        // first pool; a sphere's H2 at N = 1024 more: tools/cap_miss.py)
-        if (capacity && scale < kMaxParScale) {  // the same parallel reduction with larger pools
-            guard.unlock();
-            return run_pipeline(a, input_kind, host_or_dev, out, force_global, scale + 1, force_big, no_par, no_cap);
-        }
-        if (test_env_is("TDA_PAR_STRICT", "1"))  // tests: the parallel path itself must succeed
-            return fail(TDA_E_CAPACITY, "k_reduce_par aborted: item " + std::to_string(c.err >> 16) + " code " +
-                                            std::to_string(code));
-        guard.unlock();
-        return run_pipeline(a, input_kind, host_or_dev, out, force_global, scale, force_big, np_next, no_cap);
+            fprintf(stderr, "[tda] k_reduce_par aborted: code %llu, evictions %llu, records %llu, pools %llu / %llu keys\n", ctl.err,
+                    ctl.evictions, ctl.rec_used, ctl.rpool_used, ctl.bpool_used);
     }
-    if ((errs & ERR_LDS_SPILL) && !force_global) {
-        // a working column outgrew LDS: redo the batch with global-memory tables
-        guard.unlock();
-        return run_pipeline(a, input_kind, host_or_dev, out, true, scale, false, no_par, no_cap);
-    }
-    if ((errs & ERR_WORK_CAP) && !p.big && !test_env_is("TDA_REDUCE", "wave")) {
-        // a working column outgrew the one-wave HBM tables: full scans of a
-        // large column are the slow case, so switch to the radix-heap kernel
-        guard.unlock();
-        return run_pipeline(a, input_kind, host_or_dev, out, true, 0, true, no_par, no_cap);
-    }
-    if ((errs & ~(ERR_LDS_SPILL)) == (errs & (ERR_WORK_CAP | ERR_VPOOL_CAP)) && errs && scale < 2) {
-        // working column / reduced-column pool too small: retry with larger buffers
-        guard.unlock();
-        return run_pipeline(a, input_kind, host_or_dev, out, force_global, scale + 1, p.big, no_par, no_cap);
-    }
-    if (errs) return fail(TDA_E_CAPACITY, "device work buffer overflow:" + err_flags(errs));
-#ifdef TDA_PROF2
-    if (p.par) {  // per-wave phase cycles of the long columns (k_reduce_par, the last launch)
-        ParCtl c;
-        HIPC(hipMemcpy(&c, B + p.o_pctl, sizeof(c), hipMemcpyDeviceToHost));
-        const uint64_t nrec = std::min<uint64_t>(c.pad[2], kParDbgCap);
-        std::vector<uint64_t> d(nrec * kParP2Words);
-        if (nrec) HIPC(hipMemcpy(d.data(), B + p.o_pdbg + (size_t)kParDbgCap * 32, nrec * kParP2Words * 8, hipMemcpyDeviceToHost));
-        static const char* nm[8] = {"room+barrier", "min", "pivot+loads", "keys", "appends", "toggles", "refills", "owner"};
-        uint64_t best = ~0ull, bsteps = 0;
-        for (uint64_t i = 0; i < nrec; ++i)
-            if (d[i * kParP2Words + 2] > bsteps) bsteps = d[i * kParP2Words + 2], best = d[i * kParP2Words];
-        for (uint64_t i = 0; i < nrec; ++i) {
-            const uint64_t* r = &d[i * kParP2Words];
-            if (r[0] != best) continue;
-            uint64_t tot = 0;
-            for (int u = 0; u < 8; ++u) tot += r[3 + u];
-            fprintf(stderr, "[tda-prof2] layer %llu column %llu wave %llu: %llu steps, %.0f cycles/step:", (unsigned long long)(r[0] >> 40),
-                    (unsigned long long)(r[0] & ((1ull << 40) - 1)), (unsigned long long)r[1], (unsigned long long)r[2], (double)tot / (double)r[2]);
-            for (int u = 0; u < 8; ++u) fprintf(stderr, " %s %.0f", nm[u], (double)r[3 + u] / (double)r[2]);
-            fprintf(stderr, "\n");
-        }
-    }
-#endif
-#ifdef TDA_PROFILE
-    if (p.dense && !p.par) {
-        int arg = 0;
-        uint64_t p1max = 0;
-        for (int l = 0; l < L; ++l) {
-            if (w.hstats[l].prof[0][0] > w.hstats[arg].prof[0][0]) arg = l;
-            p1max = std::max<uint64_t>(p1max, w.hstats[l].prof[1][0]);
-        }
-        const uint64_t* q = w.hstats[arg].prof[0];
-        fprintf(stderr, "[tda-prof] dense H1 slowest layer %d adds %lld: total %llu pivot %llu (calls %llu ties %llu) cob_app %llu add_owner %llu new_pair %llu cycles; H2 phase-1 slowest wave %llu cycles\n",
-                arg, (long long)w.hstats[arg].n_adds[1], (unsigned long long)q[0], (unsigned long long)q[1], (unsigned long long)q[7],
-                (unsigned long long)q[2], (unsigned long long)q[3], (unsigned long long)q[4], (unsigned long long)q[5],
-                (unsigned long long)p1max);
-        uint64_t sc = 0, cb = 0, tt = 0, ad = 0, mx = 0, mxa = 0;
-        for (int l = 0; l < L; ++l) {
-            sc += w.hstats[l].prof[1][4];
-            cb += w.hstats[l].prof[1][5];
-            tt += w.hstats[l].prof[1][6];
-            ad += w.hstats[l].prof[1][7];
-            if (w.hstats[l].prof[1][2] > mx) {
-                mx = w.hstats[l].prof[1][2];
-                mxa = w.hstats[l].prof[1][3] & 0xFFFF;
-            }
-        }
-        {
-            const uint64_t* e = w.hstats[0].prof[4];
-            fprintf(stderr, "[tda-prof] k_prep_edges layer 0 (us from block entry): sort block thresh %.2f staged %.2f sorted %.2f end %.2f; mask blocks (max) thresh %.2f staged %.2f end %.2f\n",
-                    e[0] * 0.01, e[1] * 0.01, e[2] * 0.01, e[3] * 0.01, e[4] * 0.01, e[5] * 0.01, e[6] * 0.01);
-        }
-        {
-            const uint64_t* h = w.hstats[0].prof[3];
-            fprintf(stderr, "[tda-prof] k_h0_wave layer 0 (cycles from entry): thresh %llu prim %llu sort %llu unionfind %llu end %llu; chain staging (slowest layer) %llu\n",
-                    (unsigned long long)h[1], (unsigned long long)h[2], (unsigned long long)h[3], (unsigned long long)h[4],
-                    (unsigned long long)h[5], (unsigned long long)q[6]);
-        }
-        fprintf(stderr, "[tda-prof] H2 phase 1: all columns %llu cycles (scan %llu cob %llu), %llu adds; slowest column %llu cycles (%llu adds)\n",
-                (unsigned long long)tt, (unsigned long long)sc, (unsigned long long)cb, (unsigned long long)ad, (unsigned long long)mx,
-                (unsigned long long)mxa);
-    }
-    if (n > kSmallN) {
-        const uint64_t* h = w.hstats[0].prof[0];
-        fprintf(stderr, "[tda-prof] k_h0 layer 0 (cycles from entry): staged %llu, thresh+edges %llu, forest %llu, sort %llu, end %llu\n",
-                (unsigned long long)h[0], (unsigned long long)h[1], (unsigned long long)h[2], (unsigned long long)h[3],
-                (unsigned long long)h[4]);
-    }
-    if (p.par) {
-        {   // long-column timeline of the last k_reduce_par launch (H2's when it ran, else H1's)
-            ParCtl c;
-            HIPC(hipMemcpy(&c, B + p.o_pctl, sizeof(c), hipMemcpyDeviceToHost));
-            const uint64_t nlog = std::min<uint64_t>(c.pad[1], kParDbgCap);
-            std::vector<uint64_t> d(nlog * 4);
-            if (nlog) HIPC(hipMemcpy(d.data(), B + p.o_pdbg, nlog * 32, hipMemcpyDeviceToHost));
-            std::vector<uint64_t> order(nlog);
-            for (uint64_t i = 0; i < nlog; ++i) order[i] = i;
-            std::sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return d[x * 4 + 2] - d[x * 4 + 1] > d[y * 4 + 2] - d[y * 4 + 1]; });
-            uint64_t tend = 0;
-            for (uint64_t i = 0; i < nlog; ++i) tend = std::max(tend, d[i * 4 + 2]);
-            fprintf(stderr, "[tda-prof] k_reduce_par timeline: %llu columns of >= %llu steps; last one ends %.3f ms after the first workgroup started\n",
-                    (unsigned long long)nlog, (unsigned long long)kParDbgMinSteps, nlog ? (tend - c.pad[0]) * 1e-5 : 0.0);
-            for (uint64_t k = 0; k < std::min<uint64_t>(nlog, 12); ++k) {
-                const uint64_t i = order[k];
-                fprintf(stderr, "[tda-prof]   layer %llu column %llu: start %.3f ms, %.3f ms, %llu steps%s\n",
-                        (unsigned long long)(d[i * 4] >> 40), (unsigned long long)(d[i * 4] & ((1ull << 40) - 1)),
-                        (d[i * 4 + 1] - c.pad[0]) * 1e-5, (d[i * 4 + 2] - d[i * 4 + 1]) * 1e-5,
-                        (unsigned long long)(d[i * 4 + 3] & ~(1ull << 63)), (d[i * 4 + 3] >> 63) ? " (resumed)" : "");
-            }
-        }
-        const uint64_t* q = w.hstats[0].prof[2];
-        fprintf(stderr, "[tda-prof] k_reduce_par longest column: %llu steps, %llu cycles: front_min %llu, pivot+rows %llu, apparent adds %llu, refills %llu (%llu), owner path %llu; avg front log %llu, compactions %llu, spills %llu\n",
-                (unsigned long long)q[6], (unsigned long long)q[0], (unsigned long long)q[1], (unsigned long long)q[2], (unsigned long long)q[3],
-                (unsigned long long)q[4], (unsigned long long)((q[7] >> 16) & 0xFFFF), (unsigned long long)q[5], (unsigned long long)(q[7] & 0xFFFF),
-                (unsigned long long)((q[7] >> 32) & 0xFFFF), (unsigned long long)(q[7] >> 48));
-        const uint64_t* u = w.hstats[0].prof[3];
-        fprintf(stderr, "[tda-prof]   inside adds: keys %llu, capacity %llu, front toggles %llu, bucket appends %llu cycles; %llu record adds (%llu keys); refills moved %llu keys; wave 0 toggled %llu front / %llu back keys\n",
-                (unsigned long long)u[0], (unsigned long long)u[3], (unsigned long long)u[1], (unsigned long long)u[2],
-                (unsigned long long)u[4], (unsigned long long)u[5], (unsigned long long)u[6], (unsigned long long)(u[7] >> 32),
-                (unsigned long long)(u[7] & 0xFFFFFFFFull));
-        const uint64_t* v = w.hstats[0].prof[4];
-        fprintf(stderr, "[tda-prof]   record adds: room %llu, col_add %llu cycles, keys front %llu / all %llu; refill pass 3 %llu cycles; %llu saves (%llu keys) %llu cycles\n",
-                (unsigned long long)v[0], (unsigned long long)v[1], (unsigned long long)v[2], (unsigned long long)v[3], (unsigned long long)v[5],
-                (unsigned long long)v[6], (unsigned long long)v[7], (unsigned long long)v[4]);
-        const uint64_t* y = w.hstats[0].prof[1];
-        fprintf(stderr, "[tda-prof]   refill phases: search %llu, loads+min %llu, histogram %llu, level choice %llu, toggles %llu, appends %llu, compactions %llu cycles; %llu keys kept in front\n",
-                (unsigned long long)y[0], (unsigned long long)y[1], (unsigned long long)y[2], (unsigned long long)y[3],
-                (unsigned long long)y[4], (unsigned long long)y[5], (unsigned long long)y[6], (unsigned long long)y[7]);
-    }
-    if (p.big && !p.par)
-        for (int d = 1; d <= p.maxdim; ++d) {
-            const uint64_t* q = w.hstats[0].prof[d];
-            fprintf(stderr, "[tda-prof] big dim %d layer 0: cob0 %llu pop %llu owner_add %llu app_add %llu store %llu reset %llu total %llu cycles; owner adds %llu entries %llu, all adds %lld\n",
-                    d, (unsigned long long)q[0], (unsigned long long)q[1], (unsigned long long)q[2], (unsigned long long)q[3],
-                    (unsigned long long)q[4], (unsigned long long)q[5], (unsigned long long)q[7], (unsigned long long)(q[6] >> 40),
-                    (unsigned long long)(q[6] & ((1ull << 40) - 1)), (long long)w.hstats[0].n_adds[d]);
-        }
-    for (int d = 1; d <= p.maxdim; ++d) {
-        uint64_t mx[8] = {0};
-        int arg = 0;
-        for (int l = 0; l < L; ++l)
-            if (w.hstats[l].prof[d][7] > mx[7]) {
-                arg = l;
-                for (int i = 0; i < 8; ++i) mx[i] = w.hstats[l].prof[d][i];
-            }
-        fprintf(stderr, "[tda-prof] dim %d slowest layer %d adds %lld: scan %llu lookup %llu dec+facet %llu cob_app %llu toggles %llu reset %llu compact %llu total %llu cycles\n",
-                d, arg, (long long)w.hstats[arg].n_adds[d], (unsigned long long)mx[0], (unsigned long long)mx[1], (unsigned long long)mx[2],
-                (unsigned long long)mx[3], (unsigned long long)mx[4], (unsigned long long)mx[5], (unsigned long long)mx[6], (unsigned long long)mx[7]);
-    }
-#endif
+    const unsigned code = (unsigned)(ctl.err & 0xFFFF);
+    step = next_attempt(errs, code, c.at, c.p.big, test_env_is("TDA_PAR_STRICT", "1"), test_env_is("TDA_REDUCE", "wave"));
+    if (step.what != RetryStep::kFail) return 0;
+    if (errs & (ERR_PAR | ERR_PAR2))
+        return fail(TDA_E_CAPACITY, "k_reduce_par aborted: item " + std::to_string(ctl.err >> 16) + " code " + std::to_string(code));
+    return fail(TDA_E_CAPACITY, "device work buffer overflow:" + err_flags(errs));
+}
 
-    // remember what this shape needed (capacity / reducer retries; column caps are not
-    // remembered: a cap miss re-runs only its own layers, below, and every call starts capped)
-    if (force_global || scale || force_big || no_par) {
-        bool seen = false;
-        for (auto& m : w.retry)
-            if (m.N == p.N && m.maxdim == p.maxdim && m.input_kind == input_kind) {
-                m.force_global = m.force_global || force_global;
-                m.force_big = m.force_big || force_big;
-                m.no_par = std::max(m.no_par, no_par);
-                m.scale = std::max(m.scale, scale);
-                seen = true;
-            }
-        if (!seen) w.retry.push_back({p.N, p.maxdim, input_kind, force_global, force_big, no_par, scale});
-    }
-    std::vector<int> cap_miss;  // layers whose capped reduction missed (ERR_CAP_MISS): re-run below without caps
-    for (int l = 0; l < L; ++l)
-        if (w.hstats[l].err & ERR_CAP_MISS) cap_miss.push_back(l);
+// remember what this shape needed (capacity / reducer retries; column caps are not
+// remembered: a cap miss re-runs only its own layers, and every call starts capped)
+void remember_retry(Call& c) {
+    const Attempt& at = c.at;
+    if (!(at.force_global || at.scale || at.force_big || at.no_par)) return;
+    for (auto& m : c.w.retry)
+        if (m.N == c.p.N && m.maxdim == c.p.maxdim && m.input_kind == c.input_kind) {
+            m.at.force_global = m.at.force_global || at.force_global;
+            m.at.force_big = m.at.force_big || at.force_big;
+            m.at.no_par = std::max(m.at.no_par, at.no_par);
+            m.at.scale = std::max(m.at.scale, at.scale);
+            return;
+        }
+    Attempt kept = at;
+    kept.no_cap = false;
+    c.w.retry.push_back({c.p.N, c.p.maxdim, c.input_kind, kept});
+}
 
-    // ---- result
+// ---- result: one allocation (tda_rips.h layout guarantee): a binding copies it in one read
+ResultImpl* build_result(Call& c) {
+    const tda_rips_args& a = c.a;
+    const Plan& p = c.p;
+    Workspace& w = c.w;
+    const int n = c.n, L = c.L;
     auto* R = new ResultImpl();
     const int nd = p.maxdim + 1;
     const size_t S = (size_t)L * nd;
     size_t total = 0;
     for (int l = 0; l < L; ++l)
         for (int d = 0; d < nd; ++d) total += (size_t)std::min<int64_t>(w.hstats[l].count[d], (int64_t)p.pcap[d]);
-    // one allocation (tda_rips.h layout guarantee): a binding copies it in one read
     const size_t o_ne = 7 * S, o_idx = o_ne + L, o_thr = o_idx + 2 * total, o_bd = o_thr + (L + 1) / 2;
     R->blob.assign(o_bd + total, 0);
     int64_t* m_count = (int64_t*)R->blob.data();
@@ -2165,40 +1348,38 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
     int64_t* r_ne = (int64_t*)(R->blob.data() + o_ne);
     int64_t* r_idx = (int64_t*)(R->blob.data() + o_idx);
     float* r_bd = (float*)(R->blob.data() + o_bd);
+    // layer-major result (tda_rips.h); the device wrote each (layer, dim) segment
+    // at houtoff, in layer order (k_emit)
+    size_t e = 0;
     for (int l = 0; l < L; ++l) {
         const LayerStats& st = w.hstats[l];
         r_thr[l] = st.thresh;
         r_ne[l] = st.num_edges;
         for (int d = 0; d < nd; ++d) {
-            int64_t c = std::min<int64_t>(st.count[d], (int64_t)p.pcap[d]);
-            m_count[l * nd + d] = c;
-            m_off[l * nd + d] = w.houtoff[l * nd + d];
+            const size_t cnt = (size_t)std::min<int64_t>(st.count[d], (int64_t)p.pcap[d]);
+            m_count[l * nd + d] = (int64_t)cnt;
+            m_off[l * nd + d] = (int64_t)e;
             m_cs[l * nd + d] = st.checksum[d];
             m_all[l * nd + d] = st.all_pairs[d];
             m_cols[l * nd + d] = st.n_columns[d];
             m_res[l * nd + d] = st.n_residual[d] - st.nskip[d];
             m_add[l * nd + d] = st.n_adds[d];
+            const size_t src = (size_t)w.houtoff[l * nd + d];
+            for (size_t i = 0; i < cnt; ++i, ++e) {
+                const OutPair q = w.hout[src + i];
+                r_bd[e] = q.birth;
+                r_bd[total + e] = q.death;
+                r_idx[e] = q.birth_idx;
+                r_idx[total + e] = q.death_idx;
+            }
         }
     }
-    // layer-major result (tda_rips.h); the device wrote each (layer, dim) segment
-    // at houtoff, in layer order (k_emit)
-    {
-        size_t e = 0;
-        for (int l = 0; l < L; ++l)
-            for (int d = 0; d < nd; ++d) {
-                const size_t src = (size_t)w.houtoff[l * nd + d];
-                const size_t c = (size_t)m_count[l * nd + d];
-                m_off[l * nd + d] = (int64_t)e;
-                for (size_t i = 0; i < c; ++i, ++e) {
-                    const OutPair q = w.hout[src + i];
-                    r_bd[e] = q.birth;
-                    r_bd[total + e] = q.death;
-                    r_idx[e] = q.birth_idx;
-                    r_idx[total + e] = q.death_idx;
-                }
-            }
-    }
-    if (a.want_dist) {  // landed by the async copies behind the call (synchronised above)
+    tda_rips_result& o = R->pub;
+    o.L = L;
+    o.maxdim = p.maxdim;
+    o.N = n;
+    point_result(*R, total);
+    if (a.want_dist) {  // landed by the async copies behind the call (synchronised by the caller)
         R->dist.resize((size_t)L * n * n);
         std::memcpy(R->dist.data(), w.hdist, sizeof(float) * L * n * n);
     }
@@ -2206,114 +1387,165 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
         R->dist64.resize((size_t)L * n * n);
         std::memcpy(R->dist64.data(), w.hdist + sizeof(float) * L * n * n, sizeof(double) * L * n * n);
     }
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, w.ev0, w.ev1);
-    tda_rips_result& o = R->pub;
-    o.L = L;
-    o.maxdim = p.maxdim;
-    o.N = n;
-    o.count = m_count;
-    o.offset = m_off;
-    o.birth = r_bd;
-    o.death = r_bd + total;
-    o.birth_idx = r_idx;
-    o.death_idx = r_idx + total;
-    o.thresh = r_thr;
-    o.num_edges = r_ne;
-    o.blob = R->blob.data();
-    o.blob_bytes = (int64_t)(R->blob.size() * 8);
-    o.n_pairs = (int64_t)total;
-    o.checksum = m_cs;
-    o.n_all_pairs = m_all;
-    o.n_columns = m_cols;
-    o.n_residual = m_res;
-    o.n_adds = m_add;
     o.dist = a.want_dist ? R->dist.data() : nullptr;
     o.dist64 = p.want64 ? R->dist64.data() : nullptr;
-    if (nls) {
-        R->sil.assign((const double*)(w.hsil + sil_out_off), (const double*)(w.hsil + sil_out_off) + (size_t)L * nls);
+    o.silhouette = nullptr;
+    if (c.nls) {
+        R->sil.assign((const double*)(w.hsil + c.sil_out_off), (const double*)(w.hsil + c.sil_out_off) + (size_t)L * c.nls);
         o.silhouette = R->sil.data();
-    } else {
-        o.silhouette = nullptr;
     }
-    if (want_tn) {
+    o.twonn = nullptr;
+    if (c.want_tn) {
         R->tn.assign(w.htn, w.htn + L);
         o.twonn = R->tn.data();
-    } else {
-        o.twonn = nullptr;
     }
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, w.ev0, w.ev1);
     o.device_ms = ms;
-    for (size_t i = 0; i < tm.names.size(); ++i) {
-        float t = 0.0f;
-        (void)hipEventElapsedTime(&t, w.stage_ev[i], w.stage_ev[i + 1]);
-        R->stage_ms.push_back(t);
-        R->stage_name.push_back(tm.names[i]);
-    }
-    for (size_t i = 0; i < tm2.names.size(); ++i) {  // side stream: H0, edge classes
-        float t = 0.0f;
-        (void)hipEventElapsedTime(&t, w.stage_ev2[i], w.stage_ev2[i + 1]);
-        R->stage_ms.push_back(t);
-        R->stage_name.push_back(tm2.names[i]);
-    }
-    for (size_t i = 0; i < tm4.names.size(); ++i) {  // fourth stream: H0
-        float t = 0.0f;
-        (void)hipEventElapsedTime(&t, w.stage_ev4[i], w.stage_ev4[i + 1]);
-        R->stage_ms.push_back(t);
-        R->stage_name.push_back(tm4.names[i]);
-    }
-    for (size_t i = 0; i < tm3.names.size(); ++i) {  // third stream: H2 phase 1
-        float t = 0.0f;
-        (void)hipEventElapsedTime(&t, w.stage_ev3[i], w.stage_ev3[i + 1]);
-        R->stage_ms.push_back(t);
-        R->stage_name.push_back(tm3.names[i]);
-    }
+    // stage times: main stream, then stream2 (edge classes), stream4 (H0), stream3 (H2 columns, phase 1)
+    for (const StageTimer* t : {&c.tm, &c.tm2, &c.tm4, &c.tm3})
+        for (size_t i = 0; i < t->names.size(); ++i) {
+            float ts = 0.0f;
+            (void)hipEventElapsedTime(&ts, t->ev[i], t->ev[i + 1]);
+            R->stage_ms.push_back(ts);
+            R->stage_name.push_back(t->names[i]);
+        }
     o.n_stages = (int32_t)R->stage_name.size();
-    if (host_prof) {
+    o.stage_name = R->stage_name.data();
+    o.stage_ms = R->stage_ms.data();
+    o.n_cap_reruns = 0;
+    return R;
+}
+
+// TDA_HOST_PROF=1: host-side time of the call's parts (stderr, every 200 calls)
+struct HostProf {
+    using clk = std::chrono::steady_clock;
+    clk::time_point entry, h0, h1, h2;
+    void add(float device_ms) const {
         static double acc[5] = {0, 0, 0, 0, 0};
         static int calls = 0;
-        const auto h3 = hclk::now();
-        auto us = [](hclk::duration d) { return std::chrono::duration<double, std::micro>(d).count(); };
+        const auto h3 = clk::now();
+        auto us = [](clk::duration d) { return std::chrono::duration<double, std::micro>(d).count(); };
         acc[0] += us(h1 - h0);
         acc[1] += us(h2 - h1);
         acc[2] += us(h3 - h2);
-        acc[3] += ms * 1e3;
-        acc[4] += us(h0 - h_entry);
+        acc[3] += device_ms * 1e3;
+        acc[4] += us(h0 - entry);
         if (++calls % 200 == 0) {
             fprintf(stderr, "[tda-host] per call: setup %.1f us, launch %.1f us, sync %.1f us (device %.1f us), result %.1f us\n",
                     acc[4] / 200, acc[0] / 200, acc[1] / 200, acc[3] / 200, acc[2] / 200);
             acc[0] = acc[1] = acc[2] = acc[3] = acc[4] = 0;
         }
     }
-    o.stage_name = R->stage_name.data();
-    o.stage_ms = R->stage_ms.data();
-    o.n_cap_reruns = 0;
+};
+
+// One attempt of a call with the configuration `at`: plan, buffers, inputs, the launch sequence,
+// one synchronisation, then either the result (*out) or, in `step`, the attempt to run next.
+int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev, tda_rips_result** out, const Attempt& at,
+                 RetryStep& step) {
+    HostProf hp;
+    hp.entry = HostProf::clk::now();
+    HIPC(hipSetDevice(a.device));
+    Workspace& w = *get_ws(a.device, a.slot);
+    std::unique_lock<std::mutex> guard(w.mu);  // released on return: a retry or a cap-miss re-run takes it again
+    Call c(a, input_kind, host_or_dev, at, w);
+    Plan& p = c.p;
+    p.L = a.L;
+    p.N = a.N;
+    p.D = a.D;
+    p.maxdim = a.maxdim;
+    p.dtype = a.dtype;
+    p.is_dist = input_kind != 0;
+    p.want64 = input_kind == 0 && a.dtype == TDA_F64 && a.want_dist && (a.flags & TDA_FLAG_DIST64);
+    make_plan(p, at);
+    {
+        std::lock_guard<std::mutex> rt_lock(g_capture_mu);  // buffers in place; a capture re-takes it
+        if (int rc = prepare_buffers(c)) return rc;
+    }
+    if (int rc = stage_inputs(c)) return rc;
+    hipStream_t s = c.s;
+    const int n = c.n, L = c.L;
+
+    StreamSwap swap_guard{w, w.stream2, w.stream3, w.stream4, c.serial_stages};
+    if (c.serial_stages) w.stream2 = w.stream3 = w.stream4 = s;
+    c.tm.s = s, c.tm2.s = w.stream2, c.tm3.s = w.stream3, c.tm4.s = w.stream4;
+    c.tm.on = c.tm2.on = c.tm3.on = c.tm4.on = (a.flags & TDA_FLAG_STAGE_TIMES) != 0;
+    if (c.serial_stages) c.tm2.fwd = c.tm3.fwd = c.tm4.fwd = &c.tm;
+    GraphKey gk;
+    fill_graph_key(c, gk);
+
+    static const bool host_prof = getenv_is("TDA_HOST_PROF", "1");
+    hp.h0 = HostProf::clk::now();
+    if (p.piv2_sparse) {  // first use of the region, or the last call left it dirty: one full memset
+        char* pv2 = c.B + p.o_piv[2];
+        const size_t bytes = (size_t)L * p.piv_words[2] * 4;
+        if (w.piv2_dirty || w.piv2_ptr != pv2 || w.piv2_bytes < bytes) {
+            HIPC(hipMemsetAsync(pv2, 0, bytes, s));
+            w.piv2_ptr = pv2;
+            w.piv2_bytes = bytes;
+        }
+        w.piv2_dirty = true;  // until this call has cleared the words it set
+    }
+    if (int rc = launch_or_capture(c, gk)) return rc;
+    if (a.want_dist) {
+        HIPC(hipMemcpyAsync(w.hdist, c.dist, sizeof(float) * L * n * n, hipMemcpyDeviceToHost, s));
+        if (p.want64) HIPC(hipMemcpyAsync(w.hdist + sizeof(float) * L * n * n, c.B + p.o_d64, sizeof(double) * L * n * n, hipMemcpyDeviceToHost, s));
+    }
+    hp.h1 = HostProf::clk::now();
+    // (an event sync or a busy-polled end event measured the same for one call at a time, r02; and
+    // for six pipelined slots, hipStreamQuery polled in a loop: 697-701 vs 540-727 K layers/s, r06)
+    HIPC(hipStreamSynchronize(s));
+    hp.h2 = HostProf::clk::now();
+
+    int errs = 0;
+    if (int rc = collect_errors(c, errs)) return rc;
+    if (errs && getenv("TDA_DEBUG"))
+        fprintf(stderr, "[tda] N=%d L=%d errs=%s force_global=%d scale=%d\n", n, L, err_flags(errs).c_str(), (int)at.force_global, at.scale);
+    if (int rc = decide_retry(c, errs, step)) return rc;
+    if (step.what == RetryStep::kRetry) return 0;  // run_attempts runs step.next
+#ifdef TDA_PROF2
+    if (int rc = print_prof2(c)) return rc;
+#endif
+#ifdef TDA_PROFILE
+    if (int rc = print_profile(c)) return rc;
+#endif
+    remember_retry(c);
+    std::vector<int> cap_miss;  // layers whose capped reduction missed (ERR_CAP_MISS): re-run below without caps
+    for (int l = 0; l < L; ++l)
+        if (w.hstats[l].err & ERR_CAP_MISS) cap_miss.push_back(l);
+    ResultImpl* R = build_result(c);
+    if (host_prof) hp.add(R->pub.device_ms);
     if (!cap_miss.empty()) {
         guard.unlock();
-        return rerun_cap_missed(a, input_kind, host_or_dev, out, R, cap_miss, force_global, scale, force_big, no_par);
+        return rerun_cap_missed(a, input_kind, host_or_dev, out, R, cap_miss, at);
     }
     *out = &R->pub;
     return 0;
 }
 
+// the call, attempt after attempt (the workspace mutex is free between two), until the ladder
+// says done or fail
+int run_attempts(const tda_rips_args& a, int input_kind, const void* src, tda_rips_result** out, Attempt at) {
+    for (;;) {
+        RetryStep step = {RetryStep::kDone, at};
+        if (int rc = run_pipeline(a, input_kind, src, out, at, step)) return rc;
+        if (step.what != RetryStep::kRetry) return 0;
+        at = step.next;
+    }
+}
+
 // entry: start from the configuration an earlier call of this shape ended on
 int run_entry(const tda_rips_args& a, int input_kind, const void* src, tda_rips_result** out) {
-    bool fg = false, fb = false;
-    int np = 0;
-    int sc = 0;
+    Attempt at;
     // not when a test forces a reducer (the memo would override what it asks for)
     if (!test_env_is("TDA_RETRY_MEMO", "0") && !test_env("TDA_REDUCE") && !test_env("TDA_PAR") && !test_env("TDA_PAR_STRICT") &&
         !test_env("TDA_CHAIN")) {
         Workspace& w = *get_ws(a.device, a.slot);
         std::lock_guard<std::mutex> g(w.mu);
         for (const auto& m : w.retry)
-            if (m.N == a.N && m.maxdim == a.maxdim && m.input_kind == input_kind) {
-                fg = m.force_global;
-                fb = m.force_big;
-                np = m.no_par;
-                sc = m.scale;
-            }
+            if (m.N == a.N && m.maxdim == a.maxdim && m.input_kind == input_kind) at = m.at;
     }
-    return run_pipeline(a, input_kind, src, out, fg, sc, fb, np, false);
+    return run_attempts(a, input_kind, src, out, at);
 }
 
 int validate(const tda_rips_args* a) {

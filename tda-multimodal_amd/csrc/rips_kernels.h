@@ -17,6 +17,7 @@
 // many columns in flight) and rips_reduce_big.h (its fallback).
 #pragma once
 #include "rips_device.h"
+#include "rips_err.h"
 
 namespace tda {
 
@@ -49,7 +50,6 @@ struct LayerStats {  // zeroed every call; copied to the host result
     int64_t n_clr2;        // sparse-cleared H2 pivot bitmap: words k_apparent<2> listed for the end-of-call clear
     uint64_t prof[5][8];   // -DTDA_PROFILE builds: cycle counters (per dim; [3]: k_h0_wave, [4]: k_prep_layer)
 };
-enum : int32_t { ERR_RESID_CAP = 1, ERR_PAIR_CAP = 2, ERR_WORK_CAP = 4, ERR_VPOOL_CAP = 8, ERR_OUT_CAP = 16 };
 
 struct DimBufs {              // per reduction dim d (columns = d-simplices)
     const uint32_t* cleared;  // bitmap over d-simplices (per layer stride)

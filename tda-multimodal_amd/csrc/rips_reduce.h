@@ -313,8 +313,6 @@ struct ReduceAllCfg {
     uint32_t bytes;  // dynamic LDS of the launch
 };
 
-enum : int32_t { ERR_LDS_SPILL = 32, ERR_STEP_LIMIT = 64 };  // STEP_LIMIT: a column exceeded the pivot budget
-
 // residual pivot map of one dim: open addressing, key = row payload lo32.
 // lds: the table lives in LDS (typed accesses), else in HBM.
 struct PivMap {

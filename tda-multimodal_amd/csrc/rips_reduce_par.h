@@ -81,14 +81,6 @@ constexpr uint64_t kParEss = kEmpty64;        // colpiv: essential (zero column)
 constexpr uint64_t kParSkip = kEmpty64 - 1;   // colpiv: cleared column (H0 death)
 constexpr uint32_t kParSpin = 1u << 22;       // polls before a wait on another workgroup is declared hung
 
-// k_reduce_par aborted: the host re-runs the call with k_reduce_big (ERR_PAR:
-// the H1 launch aborted, both dimensions go serial; ERR_PAR2: the H2 launch
-// aborted, H1 stays parallel and H2 goes serial).  ERR_CAP_MISS (per layer): a
-// capped column ran empty below its cap; the layer's remaining columns are
-// dropped and the host re-runs that layer alone without caps.
-enum : int32_t { ERR_PAR = 128, ERR_PAR2 = 256, ERR_CAP_MISS = 512 };
-
-
 struct ParCtl {  // zeroed by k_par_init
     unsigned long long next;     // next fresh item
     unsigned long long rq_head, rq_tail;
