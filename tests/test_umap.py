@@ -1,13 +1,33 @@
 """UMAP: the embedding step before ripser
-(debug_tda_pipeline.py:96-104).  umap-learn is absent, so parity is
-distributional -- "parity unpinned" for the layout itself:
+(debug_tda_pipeline.py:96-104).  umap-learn is absent, so the kernels are
+compared with restatements of its algorithm, plus distribution-level checks:
   * the fuzzy graph (kNN, smooth_knn_dist, memberships, fuzzy union, pruning)
     against oracle/umap_ref.py, a restatement of umap's formulas (atol 2e-5:
     f32 distances on the GPU, f64 in the restatement);
   * the layout: determinism for a seed, batch == single layer, neighbourhood
     preservation and cluster separation on activation-like clustered clouds
     (the reference's 6 colours x 6 shapes = 36 prompts), and the
-    UMAP -> ripser -> record flow of the reference loop.
+    UMAP -> ripser -> record flow of the reference loop;
+  * the layout kernels against oracle/umap_ref.py's float64 restatement of
+    what csrc/umap_kernels.h states (random and spectral init, the fit SGD,
+    the transform SGD).  Each kernel is isolated through the public API: a
+    run at learning_rate 0 returns the GPU's own initial layout (alpha is 0,
+    nothing moves) and return_graph the GPU's own pruned graph; both go into
+    the restatement, whose result a second GPU run at the real rate must
+    match.  SGD growth is chaotic, so every SGD case's tolerance is measured
+    from the restatement alone: sens = the largest change of its result when
+    every start coordinate moves one f32 ulp (three random directions), tol =
+    16 sens + 2e-6, capped at 1e-3; a 0.1 % error in b, a 1 % error in the
+    repulsion strength and another negative-sample stream must each move the
+    restatement by more than 10 tol (test_sgd_reference_power, no GPU).
+
+Known deviation, documented and not tested: on a disconnected graph -- the
+reference's own arguments give one (36 clustered prompts at n_neighbors 6:
+six components, eigenvalue 1 of D^-1/2 S D^-1/2 six times) -- k_umap_spectral
+drops "column 0" of the Ritz vectors as the trivial one and returns an
+arbitrary basis of that eigenspace, where umap-learn lays the components out
+separately.  The spectral tests therefore use connected inputs with
+separated eigenvalues, and assert both.
 """
 import numpy as np
 import pytest
@@ -181,3 +201,278 @@ def test_transform_reference_flow_fit_last_layer(pkg, built_lib):
     rec = [pkg.get_max_persistence(r.dgms[1]) for r in res]
     assert len(rec) == L and all(np.isfinite(v) for v in rec)
     assert all(int(np.isinf(r.dgms[0][:, 1]).sum()) == 1 for r in res)  # one component per layer
+
+
+# ---------------------------------------------------------------- layout vs the float64 restatement
+# mix64 / umap_hash of csrc/rips_device.h and csrc/umap_kernels.h, compiled as
+# host code into a small program once: (a, b, umap_hash(a, b))
+HASH_VECTORS = [
+    (0x0, 0x0, 0xCAB120FEF3A2D79B),
+    (0x2A, 0x0, 0xD0D2047DC2E38E9C),
+    (0x2A, 0x1, 0x563AD6329112B9AF),
+    (0x2A, 0x100000703, 0x2A9FFA90AC8F1713),  # a negative-sample key: epoch 1, edge 7, sample 3
+    (0x2B, 0x3D0DBB, 0x66BDFA713C065B3A),  # a uniform-draw key: stream 4, element 1199
+    (0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFF, 0x3388A869888EBD52),
+    (0x7, 0x8000000000000000, 0x910A0A326F3B1BD0),
+]
+
+
+def test_umap_hash_vectors():
+    for a, b, h in HASH_VECTORS:
+        assert int(umap_ref.umap_hash(a, b)) == h, (hex(a), hex(b))
+    got = umap_ref.umap_hash(0x2A, np.array([0, 1, 0x100000703]))
+    assert [int(v) for v in got] == [h for a, _, h in HASH_VECTORS[1:4]]
+    u = umap_ref.rnd_unit(0x2B, 4, 1199)
+    assert float(u) == (0x66BDFA713C065B3A >> 11) * 2.0**-53 and 0.0 <= float(u) < 1.0
+
+
+def test_sgd_fit_known_small_answer():
+    """Three points P0 = (0, 0), P1 = (1, 0), P2 = (1, 2); edges 0-1 and 1-2 of
+    weight 1 (four directed edges, epochs_per_sample 1); a = b = 1, lr 1,
+    2 epochs, negative_sample_rate 1.
+    Epoch 0: every edge's next sample is at epoch 1 -- nothing moves.
+    Epoch 1: alpha = 1 - 1/2 = 0.5; the first negative sample is due at epoch
+    1 too and (1 - 1) / 1 = 0 of them are drawn.  The attraction coefficient
+    is -2 a b d2^(b-1) / (a d2^b + 1) = -2 / (d2 + 1):
+      0-1: d2 = 1, coefficient -1; head 0 moves alpha * -1 * (P0 - P1) =
+           (+0.5, 0) and tail 1 (-0.5, 0); the directed twin 1-0 does the
+           same again: P0 += (1, 0), P1 += (-1, 0);
+      1-2: d2 = 4, coefficient -0.4; head 1 moves 0.5 * -0.4 * (0, -2) =
+           (0, +0.4), tail 2 (0, -0.4); twice: P1 += (0, 0.8), P2 += (0, -0.8).
+    Result: P0 = (1, 0), P1 = (0, 0.8), P2 = (1, 1.2), each move rounded to
+    2^-40 and the sum to f32."""
+    S = np.zeros((3, 3), np.float32)
+    S[0, 1] = S[1, 0] = S[1, 2] = S[2, 1] = 1.0
+    E0 = np.array([[0, 0], [1, 0], [1, 2]], np.float32)
+    got = umap_ref.sgd_fit(S, E0, 2, 1.0, 1.0, lr=1.0, gamma=1.0, neg_rate=1, seed=42)
+    want = np.array([[1.0, 0.0], [0.0, 0.8], [1.0, 1.2]])
+    assert got.dtype == np.float32 and np.max(np.abs(got - want)) <= 2.0**-22  # 2 f32 ulps at 1.2
+    # one epoch only: nothing is sampled at epoch 0
+    assert np.array_equal(umap_ref.sgd_fit(S, E0, 1, 1.0, 1.0, neg_rate=1), E0)
+
+
+def spectral_cloud(which):
+    """Connected euclidean inputs with separated low eigenvalues (asserted by
+    spectral_preconditions): 50 points of N(0, diag(3, 2, 1)) for n_neighbors
+    8, and two layers of 130 points of N(0, diag(4, 3, 2, 1, 1)) for 10."""
+    if which == 50:
+        return (np.random.default_rng(6).standard_normal((1, 50, 3)) * np.sqrt([3, 2, 1])).astype(np.float32)
+    return (np.random.default_rng(5).standard_normal((2, 130, 5)) * np.sqrt([4, 3, 2, 1, 1])).astype(np.float32)
+
+
+# name: (clouds (L, N, D), metric, n_neighbors, n_components, n_epochs, learning_rate, negative_sample_rate,
+#        repulsion_strength, init)
+def fit_case(name):
+    if name == "a-36-5ep":
+        return clustered(1, d=64)[0], "cosine", 6, 3, 5, 1.0, 5, 1.0, "random"
+    if name == "b-36-200ep":  # a long schedule: the nxt / nxn bookkeeping and the alpha decay
+        return clustered(1, d=64)[0], "cosine", 6, 3, 200, 0.02, 5, 1.0, "random"
+    if name == "c-400":  # more than 1024 edges and more than 1024 coordinates
+        return clustered(1, n_side=20, d=64)[0], "cosine", 6, 3, 5, 1.0, 5, 1.0, "random"
+    if name == "d-args-2layers":  # non-default arguments, the second layer's own edge block (lr 1 exceeds the cap)
+        return clustered(2, d=64)[0], "cosine", 6, 2, 5, 0.5, 2, 1.5, "random"
+    if name == "e-spectral-50":  # lr 1 from a spectral start comes within 2.2 x of the cap
+        return spectral_cloud(50), "euclidean", 8, 3, 5, 0.25, 5, 1.0, "spectral"
+    raise KeyError(name)
+
+
+FIT_CASES = ["a-36-5ep", "b-36-200ep", "c-400", "d-args-2layers", "e-spectral-50"]
+# name: n_epochs, learning_rate.  36 training points, n_neighbors 36 (every
+# training point is a neighbour), 2 layers of 36 new points: 1296 slots
+TRANSFORM_CASES = {"5ep": (5, 0.25), "100ep": (100, 0.05)}
+SEED = 42
+
+
+def ab_params():
+    umap = __import__("importlib").import_module("tda-multimodal_amd.umap")
+    return umap.find_ab_params(1.0, 0.1)
+
+
+def transform_inputs():
+    """Training layer and two batches of new points: another layer whose point
+    0 is the negated training point 5 (cosine distance 2 = the disconnection
+    distance: that slot is dropped), and a noisy copy of the training layer
+    (memberships from 1 down to below max / n_epochs: pruned slots)."""
+    X, _ = clustered(2, d=64, seed=11)
+    train = X[1]
+    Y = np.stack([X[0], train + np.random.default_rng(5).standard_normal(train.shape).astype(np.float32) * 0.3])
+    Y[0, 0] = -train[5]
+    return train, Y.astype(np.float32)
+
+
+def ulp_moved(E0, rng):
+    """Every coordinate one f32 ulp up or down."""
+    up = rng.integers(0, 2, E0.shape).astype(bool)
+    return np.where(up, np.nextafter(E0, np.float32(np.inf)), np.nextafter(E0, np.float32(-np.inf))).astype(np.float32)
+
+
+def sgd_tolerance(run, E0, base):
+    """(sens, tol) of one SGD case from the restatement alone: `run(E)` is the
+    restatement from the start E, `base` = run(E0)."""
+    rng = np.random.default_rng(0)
+    sens = max(float(np.max(np.abs(run(ulp_moved(E0, rng)) - base))) for _ in range(3))
+    return sens, 16.0 * sens + 2e-6  # 2e-6: two f32 ulps at magnitude <= 16
+
+
+def assert_power(run, E0, kw, what):
+    """The restatement is stable enough to pin the kernel (tol <= 1e-3) and
+    sharp enough to see a subtly wrong one (each wrong variant > 10 tol away)."""
+    base = run(E0, **kw)
+    sens, tol = sgd_tolerance(lambda E: run(E, **kw), E0, base)
+    eff = {n: float(np.max(np.abs(run(E0, **dict(kw, **ch)) - base)))
+           for n, ch in (("b * 1.001", dict(b=kw["b"] * 1.001)), ("gamma * 1.01", dict(gamma=kw["gamma"] * 1.01)),
+                         ("seed + 1", dict(seed=kw["seed"] + 1)))}
+    msg = f"{what}: sens {sens:.3g} tol {tol:.3g} wrong variants {eff}"
+    print(msg)
+    assert tol <= 1e-3, msg
+    assert min(eff.values()) > 10.0 * tol, msg
+
+
+@pytest.mark.parametrize("name", FIT_CASES)
+def test_sgd_reference_power_fit(name):
+    X, metric, k, c, ne, lr, neg, gamma, init = fit_case(name)
+    a, b = ab_params()
+    for l in range(X.shape[0]):
+        S = umap_ref.fuzzy_graph(X[l], k, metric, n_epochs=ne)
+        E0 = umap_ref.init_random(X.shape[1], c, SEED) if init == "random" else umap_ref.spectral_init(S, c, SEED)[0]
+        assert_power(lambda E, **kw: umap_ref.sgd_fit(S, E, ne, **kw), E0,
+                     dict(a=a, b=b, lr=lr, gamma=gamma, neg_rate=neg, seed=SEED), f"fit {name} layer {l}")
+
+
+@pytest.fixture(scope="module")
+def transform_ref_model():
+    """A fitted model made by the restatement alone (no GPU)."""
+    train, Y = transform_inputs()
+    a, b = ab_params()
+    S = umap_ref.fuzzy_graph(train, 6, "cosine", n_epochs=200)
+    emb = umap_ref.sgd_fit(S, umap_ref.init_random(train.shape[0], 3, SEED), 200, a, b)
+    graphs = [umap_ref.transform_graph(train, Y[l], 36, "cosine", 2.0) for l in range(2)]
+    return train, Y, emb, graphs
+
+
+@pytest.mark.parametrize("name", list(TRANSFORM_CASES))
+def test_sgd_reference_power_transform(transform_ref_model, name):
+    train, Y, emb, graphs = transform_ref_model
+    ne, lr = TRANSFORM_CASES[name]
+    a, b = ab_params()
+    for l in range(2):
+        idx, vals = graphs[l]
+        _, _, eps = umap_ref.transform_edges(idx, vals, ne)
+        if l == 0:  # the negated point's slot for training point 5 is dropped
+            assert vals[0][idx[0] == 5] == 0.0 and np.count_nonzero(vals == 0.0) == 1
+        elif ne == 5:
+            assert np.count_nonzero(eps < 0) > 100  # pruned slots
+        E0 = umap_ref.transform_init(train, emb, Y[l], 36, "cosine", 2.0)
+        assert_power(lambda E, **kw: umap_ref.sgd_transform(idx, vals, emb, E, ne, **kw), E0,
+                     dict(a=a, b=b, lr=lr, gamma=1.0, neg_rate=5, seed=SEED), f"transform {name} layer {l}")
+
+
+def spectral_preconditions(S, c):
+    """The eigenvalues mu_0 >= mu_1 >= ... of D^-1/2 S D^-1/2 that the
+    comparison needs: mu_1 .. mu_{c+1} separated (each eigenvector is then
+    defined up to sign), and the c + 3 wide subspace iteration on (M + I) / 2
+    converged for vector c after the default 300 steps."""
+    from scipy.linalg import eigh
+
+    mu = np.sort(eigh(umap_ref.normalized_graph(S), eigvals_only=True))[::-1]
+    gaps = -np.diff(mu[1:c + 2])
+    ratio = ((1.0 + mu[c + 3]) / (1.0 + mu[c])) ** 300
+    assert gaps.min() > 5e-3 and ratio < 1e-6, (gaps, ratio)
+
+
+def nearer_sign_diff(got, both):
+    """Largest difference to the restated spectral layout, each column with
+    the nearer of its two signs."""
+    return max(min(float(np.max(np.abs(got[:, d] - both[s][:, d]))) for s in range(2)) for d in range(got.shape[1]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [36, 400])
+def test_random_init_vs_restatement(pkg, built_lib, n):
+    """init='random' at learning_rate 0 is the [0, 10] min-max of the seed's
+    uniform stream; 400 x 3 coordinates take the 1024-thread loops round twice."""
+    X, _ = clustered(1, n_side=6 if n == 36 else 20, d=64)
+    got = pkg.umap.umap_batch(X, n_neighbors=6, n_components=3, metric="cosine", random_state=SEED, n_epochs=5,
+                              init="random", learning_rate=0.0)
+    want = umap_ref.init_random(n, 3, SEED)
+    diff = float(np.max(np.abs(got[0] - want)))
+    print(f"random init n {n}: max diff {diff:.3g}")
+    assert got[0].min() == 0.0 and got[0].max() == 10.0
+    assert diff <= 2e-6
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [50, 130])
+def test_spectral_init_vs_restatement(pkg, built_lib, n):
+    """init='spectral' at learning_rate 0 against eigh in f64, column by column
+    up to sign.  Tolerance: 16 x the restated layout's own rounding sensitivity
+    (eigh on the f32 matrix against f64), at most 1e-2; the noise is restated
+    exactly.  130 points run as two distinct layers."""
+    X = spectral_cloud(n)
+    k, ne = (8, 5) if n == 50 else (10, 500)
+    got, G = pkg.umap.umap_batch(X, n_neighbors=k, n_components=3, metric="euclidean", random_state=SEED, n_epochs=ne,
+                                 init="spectral", learning_rate=0.0, return_graph=True)
+    for l in range(X.shape[0]):
+        spectral_preconditions(G[l], 3)
+        want = umap_ref.spectral_init(G[l], 3, SEED)
+        sens = nearer_sign_diff(want[0], umap_ref.spectral_init(G[l], 3, SEED, np.float32))
+        tol = 16.0 * sens
+        diff = nearer_sign_diff(got[l], want)
+        msg = f"spectral init n {n} layer {l}: sens {sens:.3g} tol {tol:.3g} max diff {diff:.3g}"
+        print(msg)
+        assert tol <= 1e-2, msg
+        assert diff <= tol, msg
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", FIT_CASES)
+def test_fit_sgd_vs_restatement(pkg, built_lib, name):
+    """k_umap_sgd against sgd_fit, from the GPU's own graph and initial layout."""
+    X, metric, k, c, ne, lr, neg, gamma, init = fit_case(name)
+    a, b = ab_params()
+    kw = dict(n_neighbors=k, n_components=c, metric=metric, random_state=SEED, n_epochs=ne, init=init,
+              negative_sample_rate=neg, repulsion_strength=gamma, a=a, b=b)
+    E0, G = pkg.umap.umap_batch(X, learning_rate=0.0, return_graph=True, **kw)
+    got = pkg.umap.umap_batch(X, learning_rate=lr, **kw)
+    for l in range(X.shape[0]):
+        def run(E):
+            return umap_ref.sgd_fit(G[l], E, ne, a, b, lr=lr, gamma=gamma, neg_rate=neg, seed=SEED)
+
+        want = run(E0[l])
+        sens, tol = sgd_tolerance(run, E0[l], want)
+        diff = float(np.max(np.abs(got[l] - want)))
+        msg = f"fit sgd {name} layer {l}: sens {sens:.3g} tol {tol:.3g} max diff {diff:.3g} moved {float(np.max(np.abs(want - E0[l]))):.3g}"
+        print(msg)
+        assert tol <= 1e-3, msg
+        assert diff <= tol, msg
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(TRANSFORM_CASES))
+def test_transform_sgd_vs_restatement(pkg, built_lib, name):
+    """The SGD half of k_umap_transform against sgd_transform: a model fitted
+    on the GPU, the GPU's own initial embedding (learning_rate 0), the restated
+    bipartite graph (its kNN slots order the edges and key the negative
+    samples)."""
+    train, Y = transform_inputs()
+    ne, lr = TRANSFORM_CASES[name]
+    red = pkg.umap.UMAP(n_neighbors=6, n_components=3, min_dist=0.1, random_state=SEED, metric="cosine", n_epochs=200).fit(train)
+    kw = dict(n_neighbors=36, metric="cosine", n_epochs=ne, a=red._a, b=red._b, seed=SEED)
+    E0 = pkg.umap.umap_transform_batch(train, red.embedding_, Y, learning_rate=0.0, **kw)
+    got = pkg.umap.umap_transform_batch(train, red.embedding_, Y, learning_rate=lr, **kw)
+    assert np.all(np.isfinite(E0)) and np.all(np.isfinite(got))
+    for l in range(2):
+        idx, vals = umap_ref.transform_graph(train, Y[l], 36, "cosine", 2.0)
+        if l == 0:
+            assert vals[0][idx[0] == 5] == 0.0
+
+        def run(E):
+            return umap_ref.sgd_transform(idx, vals, red.embedding_, E, ne, red._a, red._b, lr=lr, seed=SEED)
+
+        want = run(E0[l])
+        sens, tol = sgd_tolerance(run, E0[l], want)
+        diff = float(np.max(np.abs(got[l] - want)))
+        msg = f"transform sgd {name} layer {l}: sens {sens:.3g} tol {tol:.3g} max diff {diff:.3g} moved {float(np.max(np.abs(want - E0[l]))):.3g}"
+        print(msg)
+        assert tol <= 1e-3, msg
+        assert diff <= tol, msg
