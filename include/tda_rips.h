@@ -223,6 +223,62 @@ typedef struct tda_ed_args {
 
 int tda_effective_dim(const tda_ed_args *args, float *out);
 
+/*
+ * Greedy furthest-point landmarks (ripser.py's n_perm, get_greedy_perm
+ * [upstream]) of L layers on the GPU: per layer, on the library's own f32
+ * distance matrix dm (the sklearn-exact kernels for f32 points; for
+ * distance-matrix input the upper triangle, diagonal 0),
+ *     ds = dm[0, :]; idx_perm[0] = 0
+ *     i = 1 .. n_perm-1: idx = argmax(ds) (the lowest index among equal
+ *         maxima); idx_perm[i] = idx; lambdas[i-1] = ds[idx];
+ *         ds = minimum(ds, dm[idx, :])
+ *     lambdas[n_perm-1] = max(ds)             (r_cover, the covering radius)
+ * Every output is an index or a value of dm, copied: results are exact.
+ * The landmarks' own (n_perm, n_perm) matrices stay on the device (sub_dev) so
+ * that tda_rips_batch can run on them (is_dist, x_on_device,
+ * TDA_FLAG_INPUT_READY) without a round trip over the host; N is bounded by
+ * 8192 here, the point-count limits of tda_rips_batch then apply to n_perm.
+ * The call runs on a stream of its own (not a slot's), L layers in flight,
+ * and synchronises before it returns.  Its device workspace holds the
+ * (Lc, N, N) f32 matrices of Lc layers at a time (with the staged input and
+ * the distance kernels' partial sums): Lc is the largest count whose workspace
+ * stays within TDA_GREEDY_WS_BYTES, at least one layer.
+ * Errors before any device work: n_perm < 1 or n_perm > N: TDA_E_INVALID;
+ * N > 8192: TDA_E_UNSUPPORTED; float64 POINT clouds: TDA_E_UNSUPPORTED
+ * (sklearn's row-wise and full-matrix float64 distances disagree, so there is
+ * no exact contract); distance matrices of either dtype are accepted.
+ * Added to ABI 8 (new symbols only; no existing struct changed).
+ */
+#define TDA_GREEDY_WS_BYTES (4ull << 30)
+
+typedef struct tda_greedy_args {
+    const void *x;          /* (L, N, D) points or (L, N, N) distances, host or device */
+    int32_t dtype;          /* TDA_F32 | TDA_F64 (TDA_F64: distance matrices only)  */
+    int32_t x_on_device;    /* 1: x is a device pointer on `device`                 */
+    int64_t L, N, D;        /* D ignored when is_dist                               */
+    int32_t is_dist;        /* 1: x holds (L, N, N) distance matrices (upper used)  */
+    int32_t n_perm;         /* landmarks per layer, 1 .. N                          */
+    int32_t device;         /* HIP device ordinal                                   */
+    void *stream;           /* device input is read after it; NULL = null stream    */
+    int32_t want_dperm2all; /* 1: also return the (L, n_perm, N) landmark rows      */
+} tda_greedy_args;
+
+typedef struct tda_greedy_result {
+    int64_t L, N, n_perm;
+    const int64_t *idx_perm; /* host [L][n_perm] landmark indices, idx_perm[l][0] = 0 */
+    const float *lambdas;    /* host [L][n_perm] insertion radii; the last is r_cover */
+    const float *dperm2all;  /* host [L][n_perm][N] when want_dperm2all, else NULL    */
+    const float *sub_dev;    /* DEVICE [L][n_perm][n_perm] f32 on `device`: the
+                                landmarks' distance matrices, valid until
+                                tda_greedy_free                                       */
+    int32_t device;
+    double device_ms;        /* device time of the call (HIP events)                  */
+    double select_ms;        /* of which the selection kernel (k_greedy_perm)         */
+} tda_greedy_result;
+
+int tda_greedy_perm(const tda_greedy_args *args, tda_greedy_result **out);
+void tda_greedy_free(tda_greedy_result *r);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ from ._lib import EXPORTS, LIB_PATH, build, lib  # noqa: F401
 from .pipeline import (get_max_persistence, get_persistence, layer_record, layer_record_adversarial, peak_layer,  # noqa: F401
                        run_adversarial_condition, run_sweep, write_layer_stats, write_summary_stats)
 from .umap import UMAP, umap_batch, umap_transform_batch  # noqa: F401
-from .ripser import LayerResult, SweepPipeline, persistence_pairs, ripser, ripser_batch, rips_dm, silhouette_score  # noqa: F401
+from .ripser import (GreedyPerm, LayerResult, SweepPipeline, greedy_perm, greedy_perm_batch, persistence_pairs, ripser,  # noqa: F401
+                     ripser_batch, rips_dm, silhouette_score)
 
 _sys.modules.setdefault("tda_multimodal_amd", _sys.modules[__name__])
 
@@ -24,6 +25,9 @@ __all__ = [
     "rips_dm",
     "persistence_pairs",
     "LayerResult",
+    "greedy_perm",
+    "greedy_perm_batch",
+    "GreedyPerm",
     "get_persistence",
     "get_max_persistence",
     "layer_record",

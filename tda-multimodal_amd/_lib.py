@@ -136,6 +136,37 @@ class EdArgs(ctypes.Structure):  # include/tda_rips.h tda_ed_args
     ]
 
 
+class GreedyArgs(ctypes.Structure):  # include/tda_rips.h tda_greedy_args
+    _fields_ = [
+        ("x", ctypes.c_void_p),
+        ("dtype", ctypes.c_int32),
+        ("x_on_device", ctypes.c_int32),
+        ("L", ctypes.c_int64),
+        ("N", ctypes.c_int64),
+        ("D", ctypes.c_int64),
+        ("is_dist", ctypes.c_int32),
+        ("n_perm", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("stream", ctypes.c_void_p),
+        ("want_dperm2all", ctypes.c_int32),
+    ]
+
+
+class GreedyResult(ctypes.Structure):  # include/tda_rips.h tda_greedy_result
+    _fields_ = [
+        ("L", ctypes.c_int64),
+        ("N", ctypes.c_int64),
+        ("n_perm", ctypes.c_int64),
+        ("idx_perm", _i64p),
+        ("lambdas", _f32p),
+        ("dperm2all", _f32p),
+        ("sub_dev", ctypes.c_void_p),  # device pointer: (L, n_perm, n_perm) f32, valid until tda_greedy_free
+        ("device", ctypes.c_int32),
+        ("device_ms", ctypes.c_double),
+        ("select_ms", ctypes.c_double),
+    ]
+
+
 class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
     _fields_ = [
         ("x_train", ctypes.c_void_p),
@@ -166,7 +197,7 @@ class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
 
 # every symbol declared in include/tda_rips.h and include/tda_umap.h
 EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "tda_version", "tda_device_ok",
-           "tda_effective_dim", "tda_umap_batch", "tda_umap_transform")
+           "tda_effective_dim", "tda_greedy_perm", "tda_greedy_free", "tda_umap_batch", "tda_umap_transform")
 
 _lib = None
 
@@ -278,6 +309,10 @@ def lib():
     L.tda_umap_batch.restype = ctypes.c_int
     L.tda_effective_dim.argtypes = [ctypes.POINTER(EdArgs), _f32p]
     L.tda_effective_dim.restype = ctypes.c_int
+    L.tda_greedy_perm.argtypes = [ctypes.POINTER(GreedyArgs), ctypes.POINTER(ctypes.POINTER(GreedyResult))]
+    L.tda_greedy_perm.restype = ctypes.c_int
+    L.tda_greedy_free.argtypes = [ctypes.POINTER(GreedyResult)]
+    L.tda_greedy_free.restype = None
     L.tda_umap_transform.argtypes = [ctypes.POINTER(UmapTransformArgs)]
     L.tda_umap_transform.restype = ctypes.c_int
     _lib = L

@@ -218,6 +218,44 @@ ReduceAllCfg reduce_cfg(int n, int maxdim, const uint64_t* piv_words, bool lds_m
     return c;
 }
 
+// Which kernels turn (N, D) point clouds into distances (launch_point_distances, rips_enqueue.h):
+// the scalar k_distance, or from D = kDistMfmaMinD up the FP64 MFMA Gram tiles, as K slices
+// (dsplit > 1: partial Grams + k_distance_combine) when the tiles alone leave CUs idle: aim at
+// ~3 workgroups per CU, at least 4 K chunks per slice (TDA_DIST_SPLIT=n forces n).  The slice
+// count fixes the f64 summation order, so it depends on (N, D) only -- sized for the reference's
+// 32-layer sweep (debug_tda_pipeline.py:92), never on a call's L: a layer's distances (and so
+// its diagram) are the same in a single call, a batch and every multi-GPU shard.
+struct DistSel {
+    bool mfma = false;
+    int dsplit = 1;           // K slices of k_distance_mfma (1: no split)
+    bool gram_layer = false;  // N <= 144, f32: k_gram_layer (whole upper triangle per workgroup) + combine
+    bool partials() const { return gram_layer || dsplit > 1; }  // gpart / npart buffers are needed
+};
+// D >= 32 (raw activations): Gram tiles on the FP64 matrix cores; TDA_DIST=scalar|mfma forces one (tests)
+bool dist_use_mfma(int64_t D) { return test_env_is("TDA_DIST", "mfma") || (D >= kDistMfmaMinD && !test_env_is("TDA_DIST", "scalar")); }
+DistSel dist_select(uint64_t N, int64_t D, int dtype, bool is_dist) {
+    DistSel s;
+    s.mfma = !is_dist && dist_use_mfma(D);
+    if (s.mfma && dtype == TDA_F32 && N <= (uint64_t)kGlMaxN && !test_env_is("TDA_DIST", "tiles")) {
+        // whole-layer Gram (k_gram_layer): K slices so that a 32-layer sweep runs two
+        // workgroups per CU (512), at least 8 chunks each -- again from (N, D) only.
+        // raw4096: 16 slices 94 us + combine 26 us; 8: 130 + 15; 32: 101 + 35 (r03)
+        const uint64_t chunks = ((uint64_t)D + kDmKC - 1) / kDmKC;
+        uint64_t sp = std::min<uint64_t>(16, std::max<uint64_t>(1, chunks / 8));
+        if (const char* e = test_env("TDA_DIST_SPLIT")) sp = std::max(1, atoi(e));
+        s.dsplit = (int)sp;
+        s.gram_layer = true;
+    } else if (s.mfma) {
+        constexpr uint64_t kSplitRefL = 32;
+        const uint64_t nt = (N + kDmT - 1) / kDmT, tiles = nt * (nt + 1) / 2 * kSplitRefL, chunks = ((uint64_t)D + kDmKC - 1) / kDmKC;
+        uint64_t sp = std::min<uint64_t>(8, std::max<uint64_t>(1, (768 + tiles - 1) / tiles));
+        sp = std::min<uint64_t>(sp, std::max<uint64_t>(1, chunks / 4));
+        if (const char* e = test_env("TDA_DIST_SPLIT")) sp = std::max(1, atoi(e));
+        s.dsplit = (int)sp;
+    }
+    return s;
+}
+
 int make_plan(Plan& p, const Attempt& at) {
     const bool force_global = at.force_global, force_big = at.force_big;
     const int scale = at.scale, no_par = at.no_par;
@@ -315,34 +353,14 @@ int make_plan(Plan& p, const Attempt& at) {
     };
     const size_t esz = p.dtype == TDA_F64 ? 8 : 4;
     p.o_x = take(L * N * (p.is_dist ? N : (uint64_t)std::max<int64_t>(p.D, 1)) * esz);
-    {   // split-K for the MFMA distance when its tiles leave CUs idle: aim at ~3 workgroups per CU,
-        // at least 4 K chunks per slice (TDA_DIST_SPLIT=n forces n).  The slice count fixes the f64
-        // summation order, so it depends on (N, D) only -- sized for the reference's 32-layer sweep
-        // (debug_tda_pipeline.py:92), never on this call's L: a layer's distances (and so its
-        // diagram) are the same in a single call, a batch and every multi-GPU shard.
-        const bool mfma = !p.is_dist && (test_env_is("TDA_DIST", "mfma") || (p.D >= kDistMfmaMinD && !test_env_is("TDA_DIST", "scalar")));
-        if (mfma && p.dtype == TDA_F32 && N <= (uint64_t)kGlMaxN && !test_env_is("TDA_DIST", "tiles")) {
-            // whole-layer Gram (k_gram_layer): K slices so that a 32-layer sweep runs two
-            // workgroups per CU (512), at least 8 chunks each -- again from (N, D) only.
-            // raw4096: 16 slices 94 us + combine 26 us; 8: 130 + 15; 32: 101 + 35 (r03)
-            const uint64_t chunks = ((uint64_t)p.D + kDmKC - 1) / kDmKC;
-            uint64_t sp = std::min<uint64_t>(16, std::max<uint64_t>(1, chunks / 8));
-            if (const char* e = test_env("TDA_DIST_SPLIT")) sp = std::max(1, atoi(e));
-            p.dsplit = (int)sp;
-            p.gram_layer = true;
+    {   // the distance kernels of this (N, D) and, for K slices, their partial Grams and norms
+        const DistSel ds = dist_select(N, p.D, p.dtype, p.is_dist != 0);
+        p.dsplit = ds.dsplit;
+        p.gram_layer = ds.gram_layer;
+        if (ds.partials()) {
+            const uint64_t sp = (uint64_t)ds.dsplit;
             p.o_gpart = take(L * sp * N * N * 8);
             p.o_npart = take(L * sp * N * 8);
-        } else if (mfma) {
-            constexpr uint64_t kSplitRefL = 32;
-            const uint64_t nt = (N + kDmT - 1) / kDmT, tiles = nt * (nt + 1) / 2 * kSplitRefL, chunks = ((uint64_t)p.D + kDmKC - 1) / kDmKC;
-            uint64_t sp = std::min<uint64_t>(8, std::max<uint64_t>(1, (768 + tiles - 1) / tiles));
-            sp = std::min<uint64_t>(sp, std::max<uint64_t>(1, chunks / 4));
-            if (const char* e = test_env("TDA_DIST_SPLIT")) sp = std::max(1, atoi(e));
-            p.dsplit = (int)sp;
-            if (p.dsplit > 1) {
-                p.o_gpart = take(L * sp * N * N * 8);
-                p.o_npart = take(L * sp * N * 8);
-            }
         }
     }
     p.o_dist = take(L * N * N * 4);
@@ -1159,8 +1177,7 @@ struct StreamSwap {
 void fill_graph_key(Call& c, GraphKey& gk) {
     const tda_rips_args& a = c.a;
     const Plan& p = c.p;
-    // D >= 32 (raw activations): Gram tiles on the FP64 matrix cores; TDA_DIST=scalar|mfma forces one (tests)
-    c.dist_mfma = c.input_kind == 0 && (test_env_is("TDA_DIST", "mfma") || (p.D >= kDistMfmaMinD && !test_env_is("TDA_DIST", "scalar")));
+    c.dist_mfma = c.input_kind == 0 && dist_use_mfma(p.D);
     // column caps only with ripser's default threshold (the enclosing radius: no essential
     // H1 / H2 class); a finite user threshold can leave classes essential (k_reduce_par)
     // caps also off when H2 runs on the serial k_reduce_big after a parallel H1 (TDA_PAR2=0, or an H2
@@ -1639,3 +1656,5 @@ int tda_device_ok(int32_t device) {
 #include "umap_host.h"
 // effective dimensionality (include/tda_rips.h tda_effective_dim)
 #include "ed_host.h"
+// greedy furthest-point landmarks, ripser.py's n_perm (include/tda_rips.h tda_greedy_perm)
+#include "greedy_host.h"

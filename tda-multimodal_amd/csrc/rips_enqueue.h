@@ -166,6 +166,60 @@ void wire_buffers(Call& c) {
     }
 }
 
+// ---- distances of (L, n, D) point clouds: the one kernel selection (DistSel, rips.hip) for every
+// entry that needs the sklearn-exact f32 matrix.  rowmax must be zeroed before; gpart / npart are
+// read only when sel.partials().  mark(name) closes a stage (the call's stage timer, or a no-op).
+struct DistLaunch {
+    const void* x;  // device (L, n, D), f32 or f64
+    int dtype, n;
+    int64_t D;
+    int L;
+    DistSel sel;
+    float* dist;
+    uint32_t* rowmax;
+    double *gpart, *npart, *d64;
+};
+template <class Mark>
+int launch_point_distances(hipStream_t s, const DistLaunch& d, Mark&& mark) {
+    const void* x = d.x;
+    const int n = d.n, L = d.L;
+    float* dist = d.dist;
+    uint32_t* rowmax = d.rowmax;
+    double *gpart = d.gpart, *npart = d.npart, *d64 = d.d64;
+    const int dsplit = d.sel.dsplit;
+    const bool mfma = d.sel.mfma, gram_layer = d.sel.gram_layer;
+    dim3 grid((n + 15) / 16, (n + 15) / 16, L);
+    const unsigned nt = (unsigned)((n + kDmT - 1) / kDmT);
+    const dim3 gsplit(nt * (nt + 1) / 2, L, (unsigned)dsplit);
+    const dim3 gcomb((unsigned)std::min<uint64_t>(1024, ((uint64_t)n * n + 255) / 256), L);
+    if (mfma && dsplit > 1 && d.dtype == TDA_F64) {
+        hipLaunchKernelGGL((k_distance_mfma<double, 0, true>), gsplit, dim3(256), 0, s, (const double*)x, n, (int)d.D, dist, rowmax,
+                           gpart, npart, (double*)nullptr);
+        hipLaunchKernelGGL((k_distance_combine<double, 0>), gcomb, dim3(256), 0, s, gpart, npart, dsplit, n, dist, rowmax, d64);
+        hipLaunchKernelGGL(k_rowmax, dim3((n + 3) / 4, L), dim3(256), 0, s, dist, n, rowmax);
+    } else if (mfma && (dsplit > 1 || gram_layer)) {
+        if (gram_layer)
+            hipLaunchKernelGGL(k_gram_layer, dim3((unsigned)dsplit, L), dim3(256), 0, s, (const float*)x, n, (int)d.D, gpart, npart);
+        else
+            hipLaunchKernelGGL((k_distance_mfma<float, 0, true>), gsplit, dim3(256), 0, s, (const float*)x, n, (int)d.D, dist, rowmax,
+                               gpart, npart);
+        if (int rc = mark(gram_layer ? "k_gram_layer" : "k_distance_mfma")) return rc;  // the Gram kernel alone (bench roofline): combine, row maxima: own stages
+        hipLaunchKernelGGL((k_distance_combine<float, 0>), gcomb, dim3(256), 0, s, gpart, npart, dsplit, n, dist, rowmax);
+        if (int rc = mark("k_distance_combine")) return rc;
+        hipLaunchKernelGGL(k_rowmax, dim3((n + 3) / 4, L), dim3(256), 0, s, dist, n, rowmax);
+    } else if (mfma && d.dtype == TDA_F64)
+        hipLaunchKernelGGL((k_distance_mfma<double>), dim3(nt * (nt + 1) / 2, L), dim3(256), 0, s, (const double*)x, n, (int)d.D,
+                           dist, rowmax, (double*)nullptr, (double*)nullptr, d64);
+    else if (mfma)
+        hipLaunchKernelGGL((k_distance_mfma<float>), dim3(nt * (nt + 1) / 2, L), dim3(256), 0, s, (const float*)x, n, (int)d.D,
+                           dist, rowmax, (double*)nullptr, (double*)nullptr);
+    else if (d.dtype == TDA_F64)
+        hipLaunchKernelGGL(k_distance<double>, grid, dim3(256), 0, s, (const double*)x, n, (int)d.D, dist, rowmax, d64);
+    else
+        hipLaunchKernelGGL(k_distance<float>, grid, dim3(256), 0, s, (const float*)x, n, (int)d.D, dist, rowmax);
+    return 0;
+}
+
 // ---- distances (+ row maxima for the enclosing radius)
 int enqueue_distances(Call& c) {
     const tda_rips_args& a = c.a;
@@ -181,39 +235,13 @@ int enqueue_distances(Call& c) {
             HIPC(hipMemcpyAsync(B + p.o_x, x, (size_t)L * n * p.D * c.esz, hipMemcpyHostToDevice, s));
             x = B + p.o_x;
         }
-        dim3 grid((n + 15) / 16, (n + 15) / 16, L);
-        const bool mfma = c.dist_mfma;
-        const unsigned nt = (unsigned)((n + kDmT - 1) / kDmT);
-        double* gpart = (double*)(B + p.o_gpart);
-        double* npart = (double*)(B + p.o_npart);
-        double* d64 = p.want64 ? (double*)(B + p.o_d64) : nullptr;
-        const dim3 gsplit(nt * (nt + 1) / 2, L, (unsigned)p.dsplit);
-        const dim3 gcomb((unsigned)std::min<uint64_t>(1024, ((uint64_t)n * n + 255) / 256), L);
-        if (mfma && p.dsplit > 1 && p.dtype == TDA_F64) {
-            hipLaunchKernelGGL((k_distance_mfma<double, 0, true>), gsplit, dim3(256), 0, s, (const double*)x, n, (int)p.D, dist, rowmax,
-                               gpart, npart, (double*)nullptr);
-            hipLaunchKernelGGL((k_distance_combine<double, 0>), gcomb, dim3(256), 0, s, gpart, npart, p.dsplit, n, dist, rowmax, d64);
-            hipLaunchKernelGGL(k_rowmax, dim3((n + 3) / 4, L), dim3(256), 0, s, dist, n, rowmax);
-        } else if (mfma && (p.dsplit > 1 || p.gram_layer)) {
-            if (p.gram_layer)
-                hipLaunchKernelGGL(k_gram_layer, dim3((unsigned)p.dsplit, L), dim3(256), 0, s, (const float*)x, n, (int)p.D, gpart, npart);
-            else
-                hipLaunchKernelGGL((k_distance_mfma<float, 0, true>), gsplit, dim3(256), 0, s, (const float*)x, n, (int)p.D, dist, rowmax,
-                                   gpart, npart);
-            MARK(p.gram_layer ? "k_gram_layer" : "k_distance_mfma");  // the Gram kernel alone (bench roofline): combine, row maxima: own stages
-            hipLaunchKernelGGL((k_distance_combine<float, 0>), gcomb, dim3(256), 0, s, gpart, npart, p.dsplit, n, dist, rowmax);
-            MARK("k_distance_combine");
-            hipLaunchKernelGGL(k_rowmax, dim3((n + 3) / 4, L), dim3(256), 0, s, dist, n, rowmax);
-        } else if (mfma && p.dtype == TDA_F64)
-            hipLaunchKernelGGL((k_distance_mfma<double>), dim3(nt * (nt + 1) / 2, L), dim3(256), 0, s, (const double*)x, n, (int)p.D,
-                               dist, rowmax, (double*)nullptr, (double*)nullptr, d64);
-        else if (mfma)
-            hipLaunchKernelGGL((k_distance_mfma<float>), dim3(nt * (nt + 1) / 2, L), dim3(256), 0, s, (const float*)x, n, (int)p.D,
-                               dist, rowmax, (double*)nullptr, (double*)nullptr);
-        else if (p.dtype == TDA_F64)
-            hipLaunchKernelGGL(k_distance<double>, grid, dim3(256), 0, s, (const double*)x, n, (int)p.D, dist, rowmax, d64);
-        else
-            hipLaunchKernelGGL(k_distance<float>, grid, dim3(256), 0, s, (const float*)x, n, (int)p.D, dist, rowmax);
+        DistSel sel;
+        sel.mfma = c.dist_mfma;
+        sel.dsplit = p.dsplit;
+        sel.gram_layer = p.gram_layer;
+        const DistLaunch dl = {x, p.dtype, n, p.D, L, sel, dist, rowmax, (double*)(B + p.o_gpart), (double*)(B + p.o_npart),
+                               p.want64 ? (double*)(B + p.o_d64) : nullptr};
+        if (int rc = launch_point_distances(s, dl, [&](const char* name) { return c.tm.mark(name); })) return rc;
     } else {
         const void* x = c.xsrc;
         unsigned gx = (unsigned)std::min<uint64_t>(1024, ((uint64_t)n * n + 255) / 256);

@@ -12,6 +12,9 @@ ripser.py, unpinned at README.md:28) [upstream]:
 
 ``ripser_batch`` is the layer-loop entry: (L, N, D) clouds (numpy, or a torch
 tensor already resident on the GPU) -> one result per layer, one library call.
+``ripser_batch(X, n_perm=k)`` is ripser.py's greedy subsampling: k furthest-point
+landmarks per layer chosen on the GPU (``greedy_perm_batch``), persistence on
+the landmarks only.
 """
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ class _Batch:
     """Host copies of one batched call's outputs; LayerResults are views into it."""
 
     __slots__ = ("L", "nd", "N", "pairs", "cnt", "off", "bidx", "didx", "thr", "ne", "cs", "na", "nc", "nr", "nadd", "dist", "sil",
-                 "tn", "dg", "dist64")
+                 "tn", "dg", "dist64", "ip", "rc")
 
 
 class LayerResult(tuple):
@@ -120,6 +123,21 @@ class LayerResult(tuple):
         b = self[0]
         return None if b.dist64 is None else b.dist64[self[1]]
 
+    @property
+    def idx_perm(self):
+        """Indices of the points persistence ran on: the greedy landmarks of
+        ``ripser_batch(n_perm=k)`` in selection order, else ``arange(N)``."""
+        b = self[0]
+        return np.arange(b.N) if b.ip is None else b.ip[self[1]]
+
+    @property
+    def r_cover(self) -> float:
+        """Covering radius of the landmarks (every point is within it of one;
+        the diagrams are within 2 * r_cover of the full cloud's in bottleneck
+        distance); 0.0 without subsampling."""
+        b = self[0]
+        return 0.0 if b.rc is None else float(b.rc[self[1]])
+
 
 def _arr(ptr, n, dtype):
     """Copy n elements of a library-owned C array (one memcpy, no per-element work)."""
@@ -140,6 +158,7 @@ def _unpack(res_p, want_dist: bool, n_sets: int = 0) -> tuple[list, dict]:
     (b.cnt, b.off, b.cs, b.na, b.nc, b.nr, b.nadd, b.ne, b.bidx, b.didx, b.thr,
      b.pairs) = _lib.hostviews().blob_arrays(r.blob or 0, r.blob_bytes, L, nd, total)
     b.dg = None
+    b.ip = b.rc = None  # set by ripser_batch(n_perm=k)
     b.dist = _arr(r.dist, L * N * N, np.float32).reshape(L, N, N) if want_dist and bool(r.dist) else None
     b.dist64 = _arr(r.dist64, L * N * N, np.float64).reshape(L, N, N) if want_dist and bool(r.dist64) else None
     b.tn = _arr(r.twonn, L, np.float32) if bool(r.twonn) else None
@@ -170,7 +189,8 @@ def _check_common(maxdim, coeff, do_cocycles, n_perm, metric):
     if do_cocycles:
         raise NotImplementedError("do_cocycles=True is not implemented")
     if n_perm is not None:
-        raise NotImplementedError("greedy subsampling (n_perm) is not implemented")
+        raise NotImplementedError("greedy subsampling (n_perm) is implemented by the batch entry: "
+                                  "ripser_batch(X[None], n_perm=k)[0] (INTEGRATION.md)")
     if metric != "euclidean":
         raise NotImplementedError("only metric='euclidean' is implemented")
     if int(maxdim) != maxdim or maxdim < 0:
@@ -241,7 +261,7 @@ def ripser_batch(X, maxdim: int = 1, thresh: float = np.inf, distance_matrix: bo
                  want_dist: bool = False, return_time: bool = False, stage_times: bool = False, labels=None,
                  stage_serial: bool = False, twonn: bool = False, discard_fraction: float = 0.1, eps: float = 1e-10,
                  want_dist64: bool = False, slot: int = 0, persistence: bool = True,
-                 one_stream: bool = False, input_ready: bool = False):
+                 one_stream: bool = False, input_ready: bool = False, n_perm=None):
     """Persistence of L layers in one call.
 
     X: (L, N, D) point clouds or (L, N, N) distance matrices (distance_matrix=True);
@@ -272,8 +292,22 @@ def ripser_batch(X, maxdim: int = 1, thresh: float = np.inf, distance_matrix: bo
     queue, so several slots in flight run side by side.
     persistence=False (maxdim 0 only): distances and the side metrics asked for
     (``twonn``, ``labels``) without any persistence; every diagram is empty.
+    n_perm=k: ripser.py's greedy subsampling.  k furthest-point landmarks per
+    layer are chosen on the GPU (:func:`greedy_perm_batch`) and persistence
+    runs on them alone, their distance matrices never leaving the device; N may
+    be up to 8192, the point-count limits then apply to k.  Each result's
+    ``idx_perm`` / ``r_cover`` say which points and how well they cover;
+    ``dist``, ``thresh`` and ``num_edges`` describe the landmark matrix.
+    float32 points or distance matrices only (float64 points raise
+    NotImplementedError); ``labels``, ``twonn`` and list-of-parts input raise
+    ValueError with it.
     """
     _check_common(maxdim, 2, False, None, "euclidean")
+    if n_perm is not None:
+        return _ripser_batch_landmarks(X, n_perm, maxdim=maxdim, thresh=thresh, distance_matrix=distance_matrix, device=device,
+                                       want_dist=want_dist, return_time=return_time, stage_times=stage_times, labels=labels,
+                                       stage_serial=stage_serial, twonn=twonn, want_dist64=want_dist64, slot=slot,
+                                       persistence=persistence, one_stream=one_stream, input_ready=input_ready)
     a = _lib.RipsArgs()
     parts = list(X) if isinstance(X, (list, tuple)) else None
     if parts is not None:  # ABI 6 x_parts: consecutive sweeps of one dynamically batched call
@@ -342,6 +376,140 @@ def ripser_batch(X, maxdim: int = 1, thresh: float = np.inf, distance_matrix: bo
     return (out, info) if return_time else out
 
 
+class GreedyPerm:
+    """Greedy furthest-point landmarks of L layers (:func:`greedy_perm_batch`).
+
+    ``idx_perm`` (L, k) int64: the landmarks in selection order (the first is
+    point 0); ``lambdas`` (L, k) float64 holding f32 values: insertion radii;
+    ``r_cover`` (L,) = ``lambdas[:, -1]``: the covering radius; ``dperm2all``
+    (L, k, N) float32: the landmarks' distances to every point, or None.
+    ``device_ms`` / ``select_ms``: device time of the call and, of it, of the
+    selection kernel."""
+
+    __slots__ = ("idx_perm", "lambdas", "r_cover", "dperm2all", "device_ms", "select_ms")
+
+
+class _GreedyCall:
+    """One tda_greedy_perm call; holds the library-owned result (and with it the
+    landmark matrices on the device) until close()."""
+
+    def __init__(self, X, n_perm, distance_matrix, device, want_dperm2all, input_ready=False):
+        if isinstance(X, (list, tuple)):
+            raise ValueError("n_perm needs one (L, N, D) array: input in parts is not supported with it")
+        if n_perm is None or int(n_perm) != n_perm:
+            raise ValueError("n_perm must be an integer")
+        keep, on_dev, device_p, is64, stream = _prep_input(X, input_ready)
+        L, N = int(keep.shape[0]), int(keep.shape[1])
+        if distance_matrix and keep.shape[2] != N:
+            raise ValueError("Distance matrix is not square")
+        if not 1 <= n_perm <= N:
+            raise ValueError(f"n_perm must be in [1, N = {N}]")
+        if is64 and not distance_matrix:
+            raise NotImplementedError("n_perm with float64 point clouds is not implemented (sklearn's row-wise and full "
+                                      "float64 distances disagree): pass float32 points or a distance matrix")
+        a = _lib.GreedyArgs()
+        a.x = _data_ptrs([keep], on_dev)[0]
+        a.dtype = _lib.TDA_F64 if is64 else _lib.TDA_F32
+        a.x_on_device = 1 if on_dev else 0
+        a.L, a.N, a.D = L, N, int(keep.shape[2])
+        a.is_dist = 1 if distance_matrix else 0
+        a.n_perm = int(n_perm)
+        a.device = int(device_p if on_dev else device)
+        a.stream = (stream or None) if on_dev else None
+        a.want_dperm2all = 1 if want_dperm2all else 0
+        self.lib = _lib.lib()
+        self.res = ctypes.POINTER(_lib.GreedyResult)()
+        self.L, self.N, self.k, self.device = L, N, int(n_perm), a.device
+        _lib.check(self.lib.tda_greedy_perm(ctypes.byref(a), ctypes.byref(self.res)))
+
+    def unpack(self) -> GreedyPerm:
+        r = self.res.contents
+        L, N, k = self.L, self.N, self.k
+        g = GreedyPerm()
+        g.idx_perm = _arr(r.idx_perm, L * k, np.int64).reshape(L, k)
+        g.lambdas = _arr(r.lambdas, L * k, np.float32).reshape(L, k).astype(np.float64)
+        g.r_cover = g.lambdas[:, -1].copy()
+        g.dperm2all = _arr(r.dperm2all, L * k * N, np.float32).reshape(L, k, N) if bool(r.dperm2all) else None
+        g.device_ms, g.select_ms = float(r.device_ms), float(r.select_ms)
+        return g
+
+    def close(self):
+        if self.res:
+            self.lib.tda_greedy_free(self.res)
+            self.res = ctypes.POINTER(_lib.GreedyResult)()
+
+
+def greedy_perm_batch(X, n_perm: int, distance_matrix: bool = False, device: int = 0, want_dperm2all: bool = True) -> GreedyPerm:
+    """ripser.py's ``get_greedy_perm`` for L layers in one call on the GPU.
+
+    X: (L, N, D) float32 point clouds or (L, N, N) distance matrices
+    (distance_matrix=True; upper triangle used, diagonal taken as 0), numpy or
+    a torch CUDA tensor; N <= 8192.  Per layer, on the library's own f32
+    distance matrix: start at point 0, then n_perm - 1 times take the point
+    furthest from the landmarks so far (the lowest index among equal maxima,
+    as numpy's argmax).  Returns a :class:`GreedyPerm`; every value in it is
+    copied from the distance matrix, so it equals the host loop exactly."""
+    c = _GreedyCall(X, n_perm, distance_matrix, device, want_dperm2all)
+    try:
+        return c.unpack()
+    finally:
+        c.close()
+
+
+def greedy_perm(X, n_perm: int, distance_matrix: bool = False):
+    """Single-cloud form of :func:`greedy_perm_batch`, returning ``(idx_perm,
+    lambdas, dperm2all)`` like ripser.py's ``get_greedy_perm``."""
+    X = X if _is_torch(X) else np.asarray(X)
+    if X.ndim != 2:
+        raise ValueError("X must be a 2-D array")
+    g = greedy_perm_batch(X[None], n_perm, distance_matrix=distance_matrix)
+    return g.idx_perm[0], g.lambdas[0], g.dperm2all[0]
+
+
+def _ripser_batch_landmarks(X, n_perm, maxdim, thresh, distance_matrix, device, want_dist, return_time, stage_times, labels,
+                            stage_serial, twonn, want_dist64, slot, persistence, one_stream, input_ready):
+    """ripser_batch(n_perm=k): landmarks (tda_greedy_perm), then persistence of
+    their (L, k, k) matrices where they lie on the device (tda_rips_batch with
+    is_dist, x_on_device and TDA_FLAG_INPUT_READY: the greedy call has
+    synchronised), then the landmarks' release."""
+    if labels is not None or twonn:
+        raise ValueError("labels / twonn with n_perm are not supported: on the landmarks alone they are not the "
+                         "reference's scores of the cloud")
+    if want_dist64:
+        raise NotImplementedError("want_dist64 needs float64 point clouds, which n_perm does not take")
+    c = _GreedyCall(X, n_perm, distance_matrix, device, False, input_ready)
+    try:
+        g = c.unpack()
+        a = _lib.RipsArgs()
+        a.x = c.res.contents.sub_dev
+        a.dtype = _lib.TDA_F32
+        a.x_on_device = 1
+        a.L, a.N, a.D = c.L, c.k, c.k
+        a.is_dist = 1
+        a.maxdim = int(maxdim)
+        a.thresh = float(thresh) if np.isfinite(thresh) else float("inf")
+        a.modulus = 2
+        a.device = c.device
+        a.slot = int(slot)
+        a.want_dist = 1 if want_dist else 0
+        a.flags = _lib.TDA_FLAG_INPUT_READY
+        if stage_times:
+            a.flags |= _lib.TDA_FLAG_STAGE_TIMES | (_lib.TDA_FLAG_STAGE_SERIAL if stage_serial else 0)
+        if one_stream:
+            a.flags |= _lib.TDA_FLAG_ONE_STREAM
+        if not persistence:
+            if maxdim != 0:
+                raise ValueError("persistence=False needs maxdim=0")
+            a.flags |= _lib.TDA_FLAG_NO_PERSISTENCE
+        out, info = _call_batch(a, want_dist)
+    finally:
+        c.close()
+    b = out[0][0]
+    b.ip, b.rc = g.idx_perm, g.r_cover
+    info = dict(info, greedy_device_ms=g.device_ms, greedy_select_ms=g.select_ms)
+    return (out, info) if return_time else out
+
+
 def ripser(X, maxdim: int = 1, thresh: float = np.inf, coeff: int = 2, distance_matrix: bool = False,
            do_cocycles: bool = False, metric: str = "euclidean", n_perm=None):
     """Drop-in for ``ripser.ripser`` (Vietoris-Rips persistence over Z/2).
@@ -352,6 +520,7 @@ def ripser(X, maxdim: int = 1, thresh: float = np.inf, coeff: int = 2, distance_
     float32 for float32 points, float64 for float64 points as sklearn's
     pairwise_distances returns it; the given matrix for distance_matrix=True),
     ``idx_perm`` (arange N) and ``r_cover`` (0.0).
+    ``n_perm`` raises here: the one-cloud entry is ``ripser_batch(X[None], n_perm=k)[0]``.
     """
     _check_common(maxdim, coeff, do_cocycles, n_perm, metric)
     if hasattr(X, "tocoo"):
@@ -488,6 +657,9 @@ class SweepPipeline:
         for k in ("slot", "device"):
             if k in kw:
                 raise TypeError(f"SweepPipeline picks the {k} itself; do not pass {k}=")
+        if kw.get("n_perm") is not None:
+            raise NotImplementedError("SweepPipeline does not take n_perm: the greedy stage runs outside the slots "
+                                      "(call ripser_batch(X, n_perm=k))")
 
     @staticmethod
     def _in_key(X):
