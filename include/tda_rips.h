@@ -279,6 +279,53 @@ typedef struct tda_greedy_result {
 int tda_greedy_perm(const tda_greedy_args *args, tda_greedy_result **out);
 void tda_greedy_free(tda_greedy_result *r);
 
+/*
+ * The other spectral metrics of the reference's metrics.py, on the Gram
+ * kernels and the Jacobi kernel of tda_effective_dim (same workspace, same
+ * ordering after the caller's stream, same limits: min(N, D) <= 1024 and
+ * N <= 8192 for the N rows of one matrix).
+ *
+ * tda_matrix_entropy: matrix-based Renyi entropy (matrix_entropy,
+ * metrics.py:344-399) of every matrix for n_alpha orders at once.  With the
+ * eigenvalues lambda_i of the f64 Gram matrix clamped at 0,
+ *     p_i = lambda_i / (sum lambda + eps)
+ *     |alpha - 1| < eps:  -sum xlogy(p_i, p_i)
+ *     otherwise:          log(sum p_i^alpha) / (1 - alpha)
+ * in f64, as float32 into out[item][a] (host).  The reference takes the
+ * spectrum of the N x N matrix Z Z^T; the library diagonalises the smaller
+ * side, m = min(N, D): for N > D the N - m eigenvalues it leaves out are exact
+ * zeros, which add nothing for alpha > 0.  Orders alpha <= 0 are refused
+ * (TDA_E_INVALID): there the reference's own float32 noise eigenvalues decide
+ * its answer.  1 <= n_alpha <= 16.
+ *
+ * tda_effective_dim_windows: compute_fixed_window_ed (metrics.py:47-109), the
+ * effective dimensionality of tda_effective_dim over n_windows non-overlapping
+ * windows of S / n_windows rows, as float32 into out[b][w] (host).
+ *
+ * Windows: with S % W == 0 the (B, S, D) input is read in place as
+ * (B * W, S / W, D); otherwise the first W * (S / W) rows of every item are
+ * staged with one 2-D copy.  n_windows > S is taken as n_windows = S (every
+ * row its own window; the output then has S columns); n_windows < 0, or 0 for
+ * tda_effective_dim_windows: TDA_E_INVALID.  Errors arrive before any device
+ * work.  Added to ABI 8 (new symbols only; no existing struct changed).
+ */
+typedef struct tda_spectral_args {
+    const void *x;          /* (B, S, D) row-major, host or device               */
+    int32_t dtype;          /* TDA_F32 | TDA_F64                                 */
+    int32_t x_on_device;    /* 1: x is a device pointer on `device`              */
+    int64_t B, S, D;        /* B items of S rows (tokens) by D                   */
+    int64_t n_windows;      /* 0: one matrix per item (N = S); W >= 1: W windows of
+                               S / W rows each, the last S % W rows of an item dropped */
+    int32_t n_alpha;        /* matrix entropy only: orders per call, 1 .. 16     */
+    const double *alphas;   /* matrix entropy only: host [n_alpha], each > 0     */
+    double eps;             /* matrix entropy only: metrics.py's eps (1e-10)     */
+    int32_t device;
+    void *stream;           /* device input is read after it; NULL = null stream  */
+} tda_spectral_args;
+
+int tda_matrix_entropy(const tda_spectral_args *args, float *out);        /* out[B * max(W, 1)][n_alpha] */
+int tda_effective_dim_windows(const tda_spectral_args *args, float *out); /* out[B][W] */
+
 #ifdef __cplusplus
 }
 #endif

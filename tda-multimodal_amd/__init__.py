@@ -8,7 +8,8 @@ include/tda_rips.h; no CPU fallback.
 import sys as _sys
 
 from . import distributed, metrics, synthetic, umap  # noqa: F401
-from .metrics import compute_effective_dimensionality, compute_intrinsic_dimensionality  # noqa: F401
+from .metrics import (compute_effective_dimensionality, compute_fixed_window_ed, compute_fixed_window_id,  # noqa: F401
+                      compute_intrinsic_dimensionality, matrix_entropy, matrix_entropy_profile)
 from ._lib import EXPORTS, LIB_PATH, build, lib  # noqa: F401
 from .pipeline import (get_max_persistence, get_persistence, layer_record, layer_record_adversarial, peak_layer,  # noqa: F401
                        run_adversarial_condition, run_sweep, write_layer_stats, write_summary_stats)
@@ -39,6 +40,10 @@ __all__ = [
     "silhouette_score",
     "compute_intrinsic_dimensionality",
     "compute_effective_dimensionality",
+    "compute_fixed_window_ed",
+    "compute_fixed_window_id",
+    "matrix_entropy",
+    "matrix_entropy_profile",
     "UMAP",
     "umap_batch",
     "umap_transform_batch",

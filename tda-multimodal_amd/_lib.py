@@ -136,6 +136,26 @@ class EdArgs(ctypes.Structure):  # include/tda_rips.h tda_ed_args
     ]
 
 
+class SpectralArgs(ctypes.Structure):  # include/tda_rips.h tda_spectral_args
+    _fields_ = [
+        ("x", ctypes.c_void_p),
+        ("dtype", ctypes.c_int32),
+        ("x_on_device", ctypes.c_int32),
+        ("B", ctypes.c_int64),
+        ("S", ctypes.c_int64),
+        ("D", ctypes.c_int64),
+        ("n_windows", ctypes.c_int64),
+        ("n_alpha", ctypes.c_int32),
+        ("alphas", ctypes.POINTER(ctypes.c_double)),
+        ("eps", ctypes.c_double),
+        ("device", ctypes.c_int32),
+        ("stream", ctypes.c_void_p),
+    ]
+
+
+TDA_MAX_ALPHAS = 16  # orders per tda_matrix_entropy call
+
+
 class GreedyArgs(ctypes.Structure):  # include/tda_rips.h tda_greedy_args
     _fields_ = [
         ("x", ctypes.c_void_p),
@@ -197,7 +217,8 @@ class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
 
 # every symbol declared in include/tda_rips.h and include/tda_umap.h
 EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "tda_version", "tda_device_ok",
-           "tda_effective_dim", "tda_greedy_perm", "tda_greedy_free", "tda_umap_batch", "tda_umap_transform")
+           "tda_effective_dim", "tda_effective_dim_windows", "tda_matrix_entropy", "tda_greedy_perm", "tda_greedy_free",
+           "tda_umap_batch", "tda_umap_transform")
 
 _lib = None
 
@@ -309,6 +330,10 @@ def lib():
     L.tda_umap_batch.restype = ctypes.c_int
     L.tda_effective_dim.argtypes = [ctypes.POINTER(EdArgs), _f32p]
     L.tda_effective_dim.restype = ctypes.c_int
+    L.tda_effective_dim_windows.argtypes = [ctypes.POINTER(SpectralArgs), _f32p]
+    L.tda_effective_dim_windows.restype = ctypes.c_int
+    L.tda_matrix_entropy.argtypes = [ctypes.POINTER(SpectralArgs), _f32p]
+    L.tda_matrix_entropy.restype = ctypes.c_int
     L.tda_greedy_perm.argtypes = [ctypes.POINTER(GreedyArgs), ctypes.POINTER(ctypes.POINTER(GreedyResult))]
     L.tda_greedy_perm.restype = ctypes.c_int
     L.tda_greedy_free.argtypes = [ctypes.POINTER(GreedyResult)]

@@ -12,6 +12,10 @@
 // schedule: m/2 disjoint rotations per step, applied as independent 2 x 2
 // blocks J_i^T A J_j), in LDS up to m = kEdLdsMaxM and in an HBM scratch
 // above, until the off-diagonal mass is below 1e-30 of the diagonal's.
+//
+// What is made of the spectrum is the kernel's epilogue, chosen at compile
+// time: EdRatio (the ED above) or EdRenyi (the reference's matrix_entropy,
+// metrics.py:344-399, for up to kEdMaxAlpha orders per launch).
 #pragma once
 #include "rips_device.h"
 
@@ -70,11 +74,66 @@ __device__ __forceinline__ void ed_pair(int s, int k, int M, int* p, int* q) {
     *q = a < b ? b : a;
 }
 
+// Epilogues of k_ed_jacobi: what becomes of the spectrum.  Called by every
+// thread of the workgroup once A is diagonal (the eigenvalues are A_ii);
+// block_sum is the kernel's wave64 __shfl_xor + LDS sum over the workgroup.
+
+// normalised participation ratio of the singular values sqrt(max(lambda, 0)) -> out[l]
+struct EdRatio {
+    int min_dim;
+    template <bool LDS, typename Sum>
+    __device__ __forceinline__ void operator()(const double* A, int m, int l, int t, Sum& block_sum, float* __restrict__ out) const {
+        double s1 = 0.0, s2 = 0.0;
+        for (int i = t; i < m; i += kEdT) {
+            const double lam = fmax(mld<LDS>(A, (size_t)i * m + i), 0.0);
+            s1 += sqrt(lam);
+            s2 += lam;
+        }
+        s1 = block_sum(s1);
+        s2 = block_sum(s2);
+        if (t == 0) {
+            const double pr = (s1 * s1) / fmax(s2, 1e-10);
+            out[l] = (float)(pr / fmax((double)min_dim, 1.0));
+        }
+    }
+};
+
+// matrix-based Renyi entropy of the normalised spectrum (the reference's
+// matrix_entropy, metrics.py:344-399) for n_alpha orders in one pass:
+// p_i = lambda_i / (sum lambda + eps), lambda_i = max(A_ii, 0);
+// |alpha - 1| < eps: -sum xlogy(p_i, p_i), else log(sum p_i^alpha) / (1 - alpha)
+// -> out[l][a].  Orders are > 0 (the host checks), so the N - m zero
+// eigenvalues of the larger Gram matrix that the m x m one lacks add nothing.
+constexpr int kEdMaxAlpha = 16;
+struct EdRenyi {
+    int n_alpha;
+    double eps;
+    double alpha[kEdMaxAlpha];
+    template <bool LDS, typename Sum>
+    __device__ __forceinline__ void operator()(const double* A, int m, int l, int t, Sum& block_sum, float* __restrict__ out) const {
+        double tr = 0.0;
+        for (int i = t; i < m; i += kEdT) tr += fmax(mld<LDS>(A, (size_t)i * m + i), 0.0);
+        tr = block_sum(tr) + eps;
+        for (int a = 0; a < n_alpha; ++a) {
+            const double al = alpha[a];
+            const bool shannon = fabs(al - 1.0) < eps;
+            double s = 0.0;
+            for (int i = t; i < m; i += kEdT) {
+                const double p = fmax(mld<LDS>(A, (size_t)i * m + i), 0.0) / tr;
+                if (shannon) s += p > 0.0 ? p * log(p) : 0.0;
+                else s += pow(p, al);
+            }
+            s = block_sum(s);
+            if (t == 0) out[(size_t)l * n_alpha + a] = (float)(shannon ? -s : log(s) / (1.0 - al));
+        }
+    }
+};
+
 // one workgroup per item: Jacobi eigenvalues of the m x m Gram matrix Gin[l]
-// (LDS: copied into dynamic LDS; else updated in place), then the normalised
-// participation ratio of the singular values sqrt(max(lambda, 0)) -> out[l]
-template <bool LDS>
-__global__ __launch_bounds__(kEdT) void k_ed_jacobi(double* __restrict__ Gin, int m, int min_dim, float* __restrict__ out) {
+// (LDS: copied into dynamic LDS; else updated in place), then the epilogue
+// (EdRatio or EdRenyi) on the diagonal
+template <bool LDS, typename Epi>
+__global__ __launch_bounds__(kEdT) void k_ed_jacobi(double* __restrict__ Gin, int m, Epi epi, float* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ double cs[kEdMaxM / 2], sn[kEdMaxM / 2];
     __shared__ int pp[kEdMaxM / 2], qq[kEdMaxM / 2];
@@ -161,18 +220,7 @@ __global__ __launch_bounds__(kEdT) void k_ed_jacobi(double* __restrict__ Gin, in
             __syncthreads();
         }
     }
-    double s1 = 0.0, s2 = 0.0;
-    for (int i = t; i < m; i += kEdT) {
-        const double lam = fmax(mld<LDS>(A, (size_t)i * m + i), 0.0);
-        s1 += sqrt(lam);
-        s2 += lam;
-    }
-    s1 = block_sum(s1);
-    s2 = block_sum(s2);
-    if (t == 0) {
-        const double pr = (s1 * s1) / fmax(s2, 1e-10);
-        out[l] = (float)(pr / fmax((double)min_dim, 1.0));
-    }
+    epi.template operator()<LDS>(A, m, l, t, block_sum, out);
 }
 
 }  // namespace tda
