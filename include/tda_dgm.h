@@ -1,0 +1,64 @@
+/*
+ * tda_dgm.h -- distances between persistence diagrams on the MI355X (gfx950).
+ * Part of libtda_rips.so: error codes, tda_last_error() and tda_device_ok()
+ * are those of tda_rips.h.  Added to ABI 8 (new symbols only; no existing
+ * struct changed).
+ *
+ * tda_sliced_wasserstein: the sliced Wasserstein distance (Carriere, Cuturi,
+ * Oudot 2017; persim.sliced_wasserstein [upstream]) of P pairs out of S
+ * diagrams in one call.  For diagrams A (n1 points) and B (n2 points) of
+ * (birth, death) pairs, after dropping every point with a non-finite
+ * coordinate (the essential classes):
+ *     pi(p)   = ((b + d) / 2, (b + d) / 2)            the diagonal projection
+ *     theta_i = -pi/2 + i * (pi / M),  u_i = (cos theta_i, sin theta_i)
+ *     V1_i    = {p . u_i : p in A} u {pi(q) . u_i : q in B}
+ *     V2_i    = {q . u_i : q in B} u {pi(p) . u_i : p in A}
+ *     SW(A,B) = (1 / M) * sum_{i < M} sum_k |sort(V1_i)[k] - sort(V2_i)[k]|
+ * (= (1/pi) * sum_i (pi/M) * ...), everything in float64, the directions
+ * summed in increasing i.  Two empty diagrams give 0.  The result is a pure
+ * function of the two point multisets and M: SW(A, A) is exactly 0,
+ * SW(A, B) == SW(B, A) bit for bit, and a pair's value does not depend on
+ * what else the call holds.
+ *
+ * Limits: n1 + n2 <= TDA_SW_MAX_POINTS finite points for every requested
+ * pair and 1 <= M <= TDA_SW_MAX_DIRECTIONS, else TDA_E_UNSUPPORTED;
+ * P * M <= TDA_SW_MAX_WORK per call (the (P, M) scratch buffer), else
+ * TDA_E_UNSUPPORTED: split the call.  Bad offsets or pair indices:
+ * TDA_E_INVALID.  All argument errors arrive before any device work.
+ */
+#ifndef TDA_DGM_H
+#define TDA_DGM_H
+
+#include "tda_rips.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define TDA_SW_MAX_POINTS 4096
+#define TDA_SW_MAX_DIRECTIONS 1024
+#define TDA_SW_MAX_WORK (1ll << 27)
+
+typedef struct tda_sw_args {
+    const double *points;   /* host (total, 2) f64 (birth, death); non-finite rows are skipped */
+    const int64_t *offsets; /* host [S + 1] non-decreasing row boundaries, offsets[0] = 0      */
+    int64_t S;              /* diagrams                                                        */
+    const int32_t *pairs;   /* host (P, 2) diagram indices, or NULL: every i < j, row-major    */
+    int64_t P;              /* pairs in `pairs`; ignored when pairs is NULL                    */
+    int32_t M;              /* directions, 1 .. TDA_SW_MAX_DIRECTIONS                          */
+    int32_t device;         /* HIP device ordinal                                              */
+} tda_sw_args;
+
+typedef struct tda_sw_result {
+    int64_t P;          /* pairs computed (S (S - 1) / 2 when pairs was NULL)   */
+    const double *dist; /* host [P]                                             */
+    double device_ms;   /* device time of the call (HIP events, copies included) */
+} tda_sw_result;
+
+int tda_sliced_wasserstein(const tda_sw_args *args, tda_sw_result **out);
+void tda_sw_free(tda_sw_result *r);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

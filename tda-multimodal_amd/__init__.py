@@ -7,12 +7,14 @@ include/tda_rips.h; no CPU fallback.
 """
 import sys as _sys
 
-from . import distributed, metrics, synthetic, umap  # noqa: F401
+from . import diagrams, distributed, metrics, synthetic, umap  # noqa: F401
+from .diagrams import sliced_wasserstein, sliced_wasserstein_kernel, sliced_wasserstein_matrix  # noqa: F401
 from .metrics import (compute_effective_dimensionality, compute_fixed_window_ed, compute_fixed_window_id,  # noqa: F401
                       compute_intrinsic_dimensionality, matrix_entropy, matrix_entropy_profile)
-from ._lib import EXPORTS, LIB_PATH, build, lib  # noqa: F401
-from .pipeline import (get_max_persistence, get_persistence, layer_record, layer_record_adversarial, peak_layer,  # noqa: F401
-                       run_adversarial_condition, run_sweep, write_layer_stats, write_summary_stats)
+from ._lib import DGM_EXPORTS, EXPORTS, LIB_PATH, build, lib  # noqa: F401
+from .pipeline import (get_max_persistence, get_persistence, layer_distance_matrix, layer_record,  # noqa: F401
+                       layer_record_adversarial, peak_layer, run_adversarial_condition, run_sweep, write_layer_stats,
+                       write_summary_stats)
 from .umap import UMAP, umap_batch, umap_transform_batch  # noqa: F401
 from .ripser import (GreedyPerm, LayerResult, SweepPipeline, greedy_perm, greedy_perm_batch, persistence_pairs, ripser,  # noqa: F401
                      ripser_batch, rips_dm, silhouette_score)
@@ -37,6 +39,10 @@ __all__ = [
     "run_sweep",
     "write_summary_stats",
     "peak_layer",
+    "layer_distance_matrix",
+    "sliced_wasserstein",
+    "sliced_wasserstein_matrix",
+    "sliced_wasserstein_kernel",
     "silhouette_score",
     "compute_intrinsic_dimensionality",
     "compute_effective_dimensionality",

@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/tda_rips.h (libtda_rips.so, gfx950).
+"""ctypes binding of the C ABI in include/tda_rips.h, tda_umap.h and tda_dgm.h (libtda_rips.so, gfx950).
 
 The product path has exactly one implementation: the HIP library.  If it is
 missing or no gfx950 device is visible, calls raise -- there is no CPU
@@ -187,6 +187,31 @@ class GreedyResult(ctypes.Structure):  # include/tda_rips.h tda_greedy_result
     ]
 
 
+class SwArgs(ctypes.Structure):  # include/tda_dgm.h tda_sw_args
+    _fields_ = [
+        ("points", ctypes.c_void_p),
+        ("offsets", ctypes.c_void_p),
+        ("S", ctypes.c_int64),
+        ("pairs", ctypes.c_void_p),
+        ("P", ctypes.c_int64),
+        ("M", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+    ]
+
+
+class SwResult(ctypes.Structure):  # include/tda_dgm.h tda_sw_result
+    _fields_ = [
+        ("P", ctypes.c_int64),
+        ("dist", ctypes.POINTER(ctypes.c_double)),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
+TDA_SW_MAX_POINTS = 4096  # finite points of a pair of diagrams together
+TDA_SW_MAX_DIRECTIONS = 1024
+TDA_SW_MAX_WORK = 1 << 27  # pairs x directions per call
+
+
 class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
     _fields_ = [
         ("x_train", ctypes.c_void_p),
@@ -219,6 +244,8 @@ class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
 EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "tda_version", "tda_device_ok",
            "tda_effective_dim", "tda_effective_dim_windows", "tda_matrix_entropy", "tda_greedy_perm", "tda_greedy_free",
            "tda_umap_batch", "tda_umap_transform")
+# every symbol declared in include/tda_dgm.h
+DGM_EXPORTS = ("tda_sliced_wasserstein", "tda_sw_free")
 
 _lib = None
 
@@ -340,6 +367,10 @@ def lib():
     L.tda_greedy_free.restype = None
     L.tda_umap_transform.argtypes = [ctypes.POINTER(UmapTransformArgs)]
     L.tda_umap_transform.restype = ctypes.c_int
+    L.tda_sliced_wasserstein.argtypes = [ctypes.POINTER(SwArgs), ctypes.POINTER(ctypes.POINTER(SwResult))]
+    L.tda_sliced_wasserstein.restype = ctypes.c_int
+    L.tda_sw_free.argtypes = [ctypes.POINTER(SwResult)]
+    L.tda_sw_free.restype = None
     _lib = L
     return L
 

@@ -1,0 +1,230 @@
+// dgm_host.h -- host side of tda_sliced_wasserstein (include/tda_dgm.h), part of
+// rips.hip's translation unit (shares its error state and device checks).
+//
+// One call: drop the non-finite points on the host, sort the pairs into three
+// size classes, upload everything in one copy, launch k_sw_pairs once per
+// non-empty class and k_sw_sum once, copy the P distances back.  The workspace,
+// its stream and its mutex are per device and this entry's own (no slot's
+// stream is used, nothing is captured into a graph).
+//
+// Size classes (npow = next_pow2(n1 + n2) of a pair): a launch has one
+// workgroup size and one dynamic-LDS size, and both should fit the pair.
+//   npow <= 128:   64 threads (one wave: the barriers cost nothing), 8
+//                  directions per workgroup -- a direction is a few hundred
+//                  compare-exchanges, so the copy of the points into LDS and
+//                  the workgroup's dispatch are shared among 8 of them;
+//   npow <= 1024:  256 threads, 1 direction per workgroup;
+//   npow <= 4096:  1024 threads, 1 direction per workgroup.
+// From 256 points on a direction's sort moves a hundred times the bytes of the
+// point copy through LDS, so one direction per workgroup costs nothing and
+// gives a single large pair M workgroups to spread over the CUs.  The class
+// only sets the launch shape: the values do not depend on it (dgm_kernels.h).
+#pragma once
+#include "../../include/tda_dgm.h"
+#include "dgm_kernels.h"
+
+namespace {
+
+static_assert(kSwMaxN == TDA_SW_MAX_POINTS && kSwMaxM == TDA_SW_MAX_DIRECTIONS, "tda_dgm.h and dgm_kernels.h disagree");
+
+struct SwClass {
+    int npow_max, threads, dirs_per_wg;
+};
+constexpr SwClass kSwClasses[3] = {{128, 64, 8}, {1024, 256, 1}, {kSwMaxN, 1024, 1}};
+
+struct SwWs {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    char* buf = nullptr;
+    size_t cap = 0;
+    bool attr = false;
+    std::mutex mu;
+};
+std::mutex g_sw_mu;
+std::vector<SwWs*> g_sw_ws;
+
+SwWs& sw_ws(int dev) {
+    std::lock_guard<std::mutex> g(g_sw_mu);
+    for (auto* w : g_sw_ws)
+        if (w->device == dev) return *w;
+    auto* w = new SwWs();
+    w->device = dev;
+    g_sw_ws.push_back(w);
+    return *w;
+}
+
+struct SwResultImpl {
+    tda_sw_result pub = {};
+    std::unique_ptr<double[]> dist;
+};
+
+// what the device reads, laid out on the host: one upload
+struct SwPlan {
+    std::vector<double> pts;     // (total finite, 2)
+    std::vector<int64_t> off;    // [S + 1] into pts
+    std::vector<int32_t> pairs;  // (P, 2)
+    std::vector<int32_t> order;  // [P]: pair ids, class 0 first
+    int64_t cls_cnt[3] = {0, 0, 0};
+    int cls_n[3] = {0, 0, 0};  // the largest n1 + n2 of the class
+    int64_t P = 0;
+};
+
+int sw_plan(const tda_sw_args* a, SwPlan& pl) {
+    if (!a) return fail(TDA_E_INVALID, "args is NULL");
+    if (a->S < 0) return fail(TDA_E_INVALID, "S must be >= 0");
+    if (!a->offsets) return fail(TDA_E_INVALID, "offsets is NULL");
+    if (a->M < 1) return fail(TDA_E_INVALID, "M must be >= 1");
+    if (a->M > kSwMaxM) return fail(TDA_E_UNSUPPORTED, "sliced Wasserstein: M > 1024 directions is not supported");
+    if (a->offsets[0] != 0) return fail(TDA_E_INVALID, "offsets[0] must be 0");
+    for (int64_t s = 0; s < a->S; ++s)
+        if (a->offsets[s + 1] < a->offsets[s]) return fail(TDA_E_INVALID, "offsets must be non-decreasing");
+    const int64_t total = a->offsets[a->S];
+    if (total > 0 && !a->points) return fail(TDA_E_INVALID, "points is NULL");
+    if (a->pairs && a->P < 0) return fail(TDA_E_INVALID, "P must be >= 0");
+    if (a->S > TDA_SW_MAX_WORK) return fail(TDA_E_UNSUPPORTED, "sliced Wasserstein: too many diagrams in one call");
+    const int64_t P = a->pairs ? a->P : a->S * (a->S - 1) / 2;
+    if (P > TDA_SW_MAX_WORK || P * a->M > TDA_SW_MAX_WORK) return fail(TDA_E_UNSUPPORTED, "sliced Wasserstein: P * M > 2^27 in one call is not supported (split the pairs)");
+
+    pl.off.assign((size_t)a->S + 1, 0);
+    pl.pts.reserve((size_t)total * 2);
+    for (int64_t s = 0; s < a->S; ++s) {
+        for (int64_t r = a->offsets[s]; r < a->offsets[s + 1]; ++r) {
+            const double b = a->points[2 * r], d = a->points[2 * r + 1];
+            if (!std::isfinite(b) || !std::isfinite(d)) continue;  // the essential classes
+            pl.pts.push_back(b);
+            pl.pts.push_back(d);
+        }
+        pl.off[s + 1] = (int64_t)(pl.pts.size() / 2);
+    }
+    pl.P = P;
+    pl.pairs.resize((size_t)P * 2);
+    if (a->pairs) {
+        for (int64_t q = 0; q < 2 * P; ++q) {
+            if (a->pairs[q] < 0 || a->pairs[q] >= a->S) return fail(TDA_E_INVALID, "pairs holds an index outside [0, S)");
+            pl.pairs[q] = a->pairs[q];
+        }
+    } else {
+        size_t q = 0;
+        for (int32_t i = 0; i < a->S; ++i)
+            for (int32_t j = i + 1; j < a->S; ++j) {
+                pl.pairs[q++] = i;
+                pl.pairs[q++] = j;
+            }
+    }
+    std::vector<uint8_t> cls((size_t)P);
+    for (int64_t p = 0; p < P; ++p) {
+        const int32_t i = pl.pairs[2 * p], j = pl.pairs[2 * p + 1];
+        const int64_t n = (pl.off[i + 1] - pl.off[i]) + (pl.off[j + 1] - pl.off[j]);
+        if (n > kSwMaxN)
+            return fail(TDA_E_UNSUPPORTED, "sliced Wasserstein: a pair of diagrams with more than 4096 finite points together is not supported");
+        const int c = n <= kSwClasses[0].npow_max ? 0 : n <= kSwClasses[1].npow_max ? 1 : 2;
+        cls[p] = (uint8_t)c;
+        pl.cls_cnt[c]++;
+        pl.cls_n[c] = std::max(pl.cls_n[c], (int)n);
+    }
+    pl.order.resize((size_t)P);
+    int64_t at[3] = {0, pl.cls_cnt[0], pl.cls_cnt[0] + pl.cls_cnt[1]};
+    for (int64_t p = 0; p < P; ++p) pl.order[at[cls[p]]++] = (int32_t)p;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int tda_sliced_wasserstein(const tda_sw_args* a, tda_sw_result** out) {
+    if (!out) return fail(TDA_E_INVALID, "out is NULL");
+    *out = nullptr;
+    SwPlan pl;
+    if (int rc = sw_plan(a, pl)) return rc;
+    if (!tda_device_ok(a->device)) return fail(TDA_E_NODEVICE, "no gfx950 device at ordinal " + std::to_string(a->device));
+    const size_t P = (size_t)pl.P, M = (size_t)a->M;
+    std::unique_ptr<SwResultImpl> R(new SwResultImpl());
+    R->dist.reset(new double[std::max<size_t>(P, 1)]);
+    R->pub.P = pl.P;
+    R->pub.dist = R->dist.get();
+    if (P == 0) {  // nothing to launch
+        *out = &R.release()->pub;
+        return 0;
+    }
+
+    // the direction table, computed here once so that host and device use the same directions
+    std::vector<double> dirs(2 * M);
+    const double pi = 3.14159265358979323846, step = pi / (double)a->M;
+    for (size_t i = 0; i < M; ++i) {
+        const double th = -pi / 2 + (double)i * step;
+        dirs[2 * i] = std::cos(th);
+        dirs[2 * i + 1] = std::sin(th);
+    }
+
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        const size_t r = o;
+        o = align_up(o + bytes, 256);
+        return r;
+    };
+    const size_t o_pts = take(pl.pts.size() * 8), o_off = take(pl.off.size() * 8), o_pairs = take(pl.pairs.size() * 4);
+    const size_t o_order = take(pl.order.size() * 4), o_dirs = take(dirs.size() * 8);
+    const size_t up_bytes = o;  // the uploaded part
+    const size_t o_part = take(P * M * 8), o_dist = take(P * 8);
+    std::vector<char> up(up_bytes);
+    if (!pl.pts.empty()) std::memcpy(up.data() + o_pts, pl.pts.data(), pl.pts.size() * 8);
+    std::memcpy(up.data() + o_off, pl.off.data(), pl.off.size() * 8);
+    std::memcpy(up.data() + o_pairs, pl.pairs.data(), pl.pairs.size() * 4);
+    std::memcpy(up.data() + o_order, pl.order.data(), pl.order.size() * 4);
+    std::memcpy(up.data() + o_dirs, dirs.data(), dirs.size() * 8);
+
+    HIPC(hipSetDevice(a->device));
+    SwWs& w = sw_ws(a->device);
+    std::lock_guard<std::mutex> guard(w.mu);
+    if (!w.stream) HIPC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    if (!w.ev0) {
+        HIPC(hipEventCreate(&w.ev0));
+        HIPC(hipEventCreate(&w.ev1));
+    }
+    if (!w.attr) {
+        HIPC(hipFuncSetAttribute((const void*)k_sw_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sw_lds_bytes(kSwMaxN, kSwMaxN)));
+        w.attr = true;
+    }
+    if (w.cap < o) {
+        std::lock_guard<std::mutex> g(g_capture_mu);  // allocations never beside a slot's graph capture
+        if (w.buf) HIPC(hipFree(w.buf));
+        w.buf = nullptr;
+        w.cap = 0;
+        HIPC(hipMalloc(&w.buf, o));
+        w.cap = o;
+    }
+    hipStream_t s = w.stream;
+    double* part = (double*)(w.buf + o_part);
+    double* dist = (double*)(w.buf + o_dist);
+    HIPC(hipEventRecord(w.ev0, s));
+    HIPC(hipMemcpyAsync(w.buf, up.data(), up_bytes, hipMemcpyHostToDevice, s));
+    int64_t first = 0;
+    for (int c = 0; c < 3; ++c) {
+        const int64_t cnt = pl.cls_cnt[c];
+        if (!cnt) continue;
+        const SwClass& k = kSwClasses[c];
+        const int n = pl.cls_n[c];
+        const size_t lds = sw_lds_bytes(n, (int)next_pow2((uint64_t)std::max(n, 1)));
+        const unsigned chunks = (unsigned)((a->M + k.dirs_per_wg - 1) / k.dirs_per_wg);
+        hipLaunchKernelGGL(k_sw_pairs, dim3((unsigned)cnt, chunks), dim3(k.threads), lds, s, (const double*)(w.buf + o_pts),
+                           (const int64_t*)(w.buf + o_off), (const int32_t*)(w.buf + o_pairs),
+                           (const int32_t*)(w.buf + o_order) + first, (const double*)(w.buf + o_dirs), (int)a->M, k.dirs_per_wg, part);
+        HIPC(hipGetLastError());
+        first += cnt;
+    }
+    hipLaunchKernelGGL(k_sw_sum, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const double*)part, (int64_t)P, (int)a->M, dist);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(R->dist.get(), dist, P * 8, hipMemcpyDeviceToHost, s));
+    HIPC(hipEventRecord(w.ev1, s));
+    HIPC(hipStreamSynchronize(s));
+    float ms = 0.0f;
+    HIPC(hipEventElapsedTime(&ms, w.ev0, w.ev1));
+    R->pub.device_ms = ms;
+    *out = &R.release()->pub;
+    return 0;
+}
+
+extern "C" void tda_sw_free(tda_sw_result* r) {
+    if (!r) return;
+    delete reinterpret_cast<SwResultImpl*>(r);  // pub is the first member
+}

@@ -1658,3 +1658,5 @@ int tda_device_ok(int32_t device) {
 #include "ed_host.h"
 // greedy furthest-point landmarks, ripser.py's n_perm (include/tda_rips.h tda_greedy_perm)
 #include "greedy_host.h"
+// sliced Wasserstein distances between persistence diagrams (include/tda_dgm.h)
+#include "dgm_host.h"

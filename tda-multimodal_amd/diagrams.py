@@ -1,0 +1,151 @@
+"""Distances between persistence diagrams on the GPU (include/tda_dgm.h).
+
+The reference imports ``persim`` next to ``ripser`` and uses it for
+``plot_diagrams`` only; comparing the diagrams of a sweep (layer against layer,
+condition against condition) needs a distance.  ``sliced_wasserstein`` has
+persim's signature and semantics [upstream ``persim.sliced_wasserstein(PD1,
+PD2, M=50)``]; ``sliced_wasserstein_matrix`` is the sweep-level form: every
+pair of a list of diagrams in one library call.
+
+    SW(A, B) = (1/pi) * sum_i (pi/M) * sum_k |sort(V1_i)[k] - sort(V2_i)[k]|
+
+over M directions of the half circle, V1_i / V2_i the projections of each
+diagram's points joined with the other's diagonal projections (tda_dgm.h has
+the full definition).  Everything is float64; points with a non-finite
+coordinate (the essential classes) are dropped first.  Per pair the two
+diagrams may hold 4096 finite points together, and 1 <= M <= 1024.
+"""
+from __future__ import annotations
+
+import ctypes
+import warnings
+
+import numpy as np
+
+from . import _lib
+from .ripser import LayerResult
+
+
+def _check_M(M) -> int:
+    if isinstance(M, bool) or int(M) != M:
+        raise ValueError("M must be an integer")
+    if M < 1:
+        raise ValueError("M must be >= 1")
+    if M > _lib.TDA_SW_MAX_DIRECTIONS:
+        raise NotImplementedError(f"M > {_lib.TDA_SW_MAX_DIRECTIONS} directions is not supported")
+    return int(M)
+
+
+def _flatten(dgms, dim: int):
+    """(points (total, 2) float64, offsets (S + 1,) int64) of a list of diagrams."""
+    dgms = list(dgms)
+    S = len(dgms)
+    if S and all(isinstance(r, LayerResult) for r in dgms):
+        b = dgms[0]._b
+        if not 0 <= dim < b.nd:
+            raise ValueError(f"dim = {dim}: the results hold dimensions 0 .. {b.nd - 1}")
+        if all(r._b is b for r in dgms):
+            # one batch: gather from its shared arrays, no per-layer work (pipeline.pack_results)
+            ls = np.fromiter((r._l for r in dgms), dtype=np.int64, count=S)
+            cnt, off = b.cnt[ls, dim].astype(np.int64), b.off[ls, dim].astype(np.int64)
+            offsets = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+            rows = np.repeat(off - offsets[:-1], cnt) + np.arange(int(offsets[-1]))
+            return np.ascontiguousarray(b.pairs[rows], dtype=np.float64).reshape(-1, 2), offsets
+        dgms = [r.dgms[dim] for r in dgms]
+    arrs = []
+    for d in dgms:
+        if isinstance(d, LayerResult):
+            raise ValueError("a list of diagrams holds either arrays or LayerResults, not both")
+        d = np.asarray(d, dtype=np.float64)
+        if d.size == 0:
+            d = d.reshape(0, 2)
+        if d.ndim != 2 or d.shape[1] != 2:
+            raise ValueError(f"a diagram must be an (n, 2) array of (birth, death), got shape {d.shape}")
+        arrs.append(d)
+    offsets = np.concatenate([[0], np.cumsum([len(d) for d in arrs])]).astype(np.int64)
+    points = np.concatenate(arrs) if arrs else np.zeros((0, 2))
+    return np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2), offsets
+
+
+def _finite_counts(points, offsets):
+    fin = np.isfinite(points).all(axis=1)
+    c = np.concatenate([[0], np.cumsum(fin)])
+    return c[offsets[1:]] - c[offsets[:-1]], int(len(fin) - c[-1])
+
+
+def _call(points, offsets, pairs, M: int, device: int):
+    """One tda_sliced_wasserstein call: (dist (P,), device_ms)."""
+    S = len(offsets) - 1
+    if (S < 2) if pairs is None else not len(pairs):  # no pair: nothing to launch
+        return np.zeros(0), 0.0
+    a = _lib.SwArgs()
+    a.points = points.ctypes.data if len(points) else None
+    a.offsets = offsets.ctypes.data
+    a.S = S
+    if pairs is not None:
+        a.pairs, a.P = pairs.ctypes.data, len(pairs)
+    a.M, a.device = M, int(device)
+    L = _lib.lib()
+    res = ctypes.POINTER(_lib.SwResult)()
+    _lib.check(L.tda_sliced_wasserstein(ctypes.byref(a), ctypes.byref(res)))
+    try:
+        r = res.contents
+        out = np.frombuffer(ctypes.string_at(r.dist, r.P * 8), dtype=np.float64).copy() if r.P else np.zeros(0)
+        return out, float(r.device_ms)
+    finally:
+        L.tda_sw_free(res)
+
+
+def sliced_wasserstein_matrix(dgms, M: int = 50, other=None, device: int = 0, dim: int = 1, return_time: bool = False):
+    """Sliced Wasserstein distances between every pair of diagrams, one library call.
+
+    dgms: a list of (n, 2) arrays of (birth, death), or a list of
+    :class:`LayerResult` (then diagram ``dim`` of each is taken; the results of
+    one ``ripser_batch`` call are gathered from the batch's shared arrays).
+    other: a second such list.  Returns the (S, S) float64 matrix of ``dgms``
+    against itself -- symmetric, zero diagonal -- or the (S, S') matrix of
+    ``dgms`` against ``other``; with ``return_time`` also the call's device
+    time in ms.  A pair's value is the same bits in any call that holds it."""
+    M = _check_M(M)
+    pts, off = _flatten(dgms, dim)
+    S = len(off) - 1
+    if other is None:
+        pairs = None
+        cnt, dropped = _finite_counts(pts, off)
+        top = np.sort(cnt)[-2:].sum() if S >= 2 else 0
+    else:
+        pts2, off2 = _flatten(other, dim)
+        S2 = len(off2) - 1
+        pts, off = np.concatenate([pts, pts2]), np.concatenate([off, off[-1] + off2[1:]])
+        pairs = np.stack(np.meshgrid(np.arange(S), S + np.arange(S2), indexing="ij"), -1).reshape(-1, 2).astype(np.int32)
+        cnt, dropped = _finite_counts(pts, off)
+        top = (cnt[:S].max() + cnt[S:].max()) if S and S2 else 0
+    if top > _lib.TDA_SW_MAX_POINTS:
+        raise NotImplementedError(f"a pair of diagrams holds {int(top)} finite points together: more than "
+                                  f"{_lib.TDA_SW_MAX_POINTS} is not supported")
+    if dropped:
+        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
+    dist, ms = _call(pts, off, pairs, M, device)
+    if other is None:
+        D = np.zeros((S, S))
+        iu = np.triu_indices(S, 1)  # row-major i < j: the order of the library's all-pairs result
+        D[iu] = dist
+        D = D + D.T
+    else:
+        D = dist.reshape(S, S2)
+    return (D, ms) if return_time else D
+
+
+def sliced_wasserstein(PD1, PD2, M: int = 50, device: int = 0) -> float:
+    """``persim.sliced_wasserstein(PD1, PD2, M=50)`` [upstream] on the GPU: the
+    sliced Wasserstein distance of two (n, 2) diagrams over M directions.
+    Points with a non-finite coordinate are ignored, with a warning."""
+    for d in (PD1, PD2):
+        if isinstance(d, LayerResult):
+            raise ValueError("PD1 and PD2 are (n, 2) arrays (for LayerResults: sliced_wasserstein_matrix)")
+    return float(sliced_wasserstein_matrix([PD1], M=M, other=[PD2], device=device)[0, 0])
+
+
+def sliced_wasserstein_kernel(D, sigma: float):
+    """The sliced Wasserstein kernel exp(-D / (2 sigma^2)) (Carriere, Cuturi, Oudot 2017) of distances D."""
+    return np.exp(-np.asarray(D, dtype=np.float64) / (2.0 * float(sigma) ** 2))

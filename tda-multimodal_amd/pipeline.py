@@ -28,6 +28,7 @@ import json
 
 import numpy as np
 
+from .diagrams import sliced_wasserstein_matrix
 from .ripser import ripser_batch
 
 
@@ -97,6 +98,15 @@ def run_sweep(clouds, maxdim: int = 1, thresh: float = np.inf, layer_ids=None, d
             col = sil[q]
         recs.append(layer_record(int(i), r.dgms, shp, col))
     return recs, res
+
+
+def layer_distance_matrix(results, dim: int = 1, M: int = 50, device: int = 0) -> np.ndarray:
+    """Sliced Wasserstein distances between the H_dim diagrams of a sweep's layers:
+    the (L, L) float64 matrix (symmetric, zero diagonal) of ``results``, the second
+    value ``run_sweep`` returns, in one GPU call (diagrams.sliced_wasserstein_matrix).
+    Layers of equal ``max_h1_persistence`` can hold quite different diagrams; this is
+    the layer-against-layer view the per-layer records cannot give."""
+    return sliced_wasserstein_matrix(results, M=M, device=device, dim=dim)
 
 
 ADVERSARIAL_LABELS = ("img_color", "img_shape", "txt_color", "txt_shape")
