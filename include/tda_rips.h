@@ -202,6 +202,12 @@ const char *tda_last_error(void);
 int tda_version(void);
 /* 1 if a gfx950 device is visible, 0 otherwise (never aborts). */
 int tda_device_ok(int32_t device);
+/* Test hook (host only, no device): which distance kernels (N, D) points of
+ * `dtype` run on under the current environment -- mfma: the FP64 matrix-core
+ * Gram kernels instead of the scalar one; dsplit: K slices (1: unsplit);
+ * gram_layer: the whole-layer Gram kernel (f32, N <= 144) instead of 64x64
+ * tiles.  Returns 0 or TDA_E_INVALID. */
+int tda_debug_dist_plan(int64_t N, int64_t D, int32_t dtype, int32_t *mfma, int32_t *dsplit, int32_t *gram_layer);
 
 /*
  * Normalised effective dimensionality of B activation matrices (B, N, D):

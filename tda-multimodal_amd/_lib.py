@@ -243,7 +243,7 @@ class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
 # every symbol declared in include/tda_rips.h and include/tda_umap.h
 EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "tda_version", "tda_device_ok",
            "tda_effective_dim", "tda_effective_dim_windows", "tda_matrix_entropy", "tda_greedy_perm", "tda_greedy_free",
-           "tda_umap_batch", "tda_umap_transform")
+           "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan")
 # every symbol declared in include/tda_dgm.h
 DGM_EXPORTS = ("tda_sliced_wasserstein", "tda_sw_free")
 
@@ -353,6 +353,9 @@ def lib():
     L.tda_version.restype = ctypes.c_int
     L.tda_device_ok.argtypes = [ctypes.c_int32]
     L.tda_device_ok.restype = ctypes.c_int
+    _i32p = ctypes.POINTER(ctypes.c_int32)
+    L.tda_debug_dist_plan.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _i32p, _i32p, _i32p]
+    L.tda_debug_dist_plan.restype = ctypes.c_int
     L.tda_umap_batch.argtypes = [ctypes.POINTER(UmapArgs)]
     L.tda_umap_batch.restype = ctypes.c_int
     L.tda_effective_dim.argtypes = [ctypes.POINTER(EdArgs), _f32p]

@@ -542,6 +542,7 @@ struct Workspace {
 struct GraphKey {
     int64_t L, N, D;
     int maxdim, dtype, input_kind, x_on_device, flags, force_global, scale, force_big, variant, n_label_sets, sil_K, no_par, twonn, no_cap;
+    int dsplit;  // K slices of the distance kernels (TDA_DIST_SPLIT can change them at the same (N, D): other launches, other offsets)
     float thresh, tn_eps, capf;
     double tn_discard;
     const void* x;
@@ -1200,7 +1201,9 @@ void fill_graph_key(Call& c, GraphKey& gk) {
     gk.no_cap = c.at.no_cap;
     gk.capf = c.capf;
     gk.variant = (p.dense ? 1 : 0) | (p.big ? 2 : 0) | (p.fast ? 4 : 0) | (p.lds_mode ? 8 : 0) | (p.cmode << 4) | (p.par ? 1 << 8 : 0) | (c.dist_mfma ? 1 << 9 : 0) |
-                 (p.wide ? 1 << 10 : 0) | (p.want64 ? 1 << 11 : 0) | (p.par2 ? 1 << 12 : 0) | (p.piv2_sparse ? 1 << 13 : 0);
+                 (p.wide ? 1 << 10 : 0) | (p.want64 ? 1 << 11 : 0) | (p.par2 ? 1 << 12 : 0) | (p.piv2_sparse ? 1 << 13 : 0) |
+                 (p.gram_layer ? 1 << 14 : 0);
+    gk.dsplit = p.dsplit;
     gk.thresh = a.thresh;
     gk.n_label_sets = c.nls;
     gk.sil_K = c.sil_K;  // baked into the k_silhouette launch (argument K and its LDS size)
@@ -1641,6 +1644,18 @@ void tda_rips_free(tda_rips_result* r) {
 const char* tda_last_error(void) { return g_err.c_str(); }
 
 int tda_version(void) { return TDA_RIPS_ABI_VERSION; }
+
+// test hook: the kernels dist_select() picks for (N, D, dtype) points under the current
+// environment (the TDA_TEST_OVERRIDES gate included); host only, no device
+int tda_debug_dist_plan(int64_t N, int64_t D, int32_t dtype, int32_t* mfma, int32_t* dsplit, int32_t* gram_layer) {
+    if (N < 1 || D < 0 || (dtype != TDA_F32 && dtype != TDA_F64) || !mfma || !dsplit || !gram_layer)
+        return fail(TDA_E_INVALID, "tda_debug_dist_plan: bad arguments");
+    const DistSel s = dist_select((uint64_t)N, D, dtype, false);
+    *mfma = s.mfma ? 1 : 0;
+    *dsplit = s.dsplit;
+    *gram_layer = s.gram_layer ? 1 : 0;
+    return 0;
+}
 
 int tda_device_ok(int32_t device) {
     int cnt = 0;

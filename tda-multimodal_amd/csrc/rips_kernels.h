@@ -170,6 +170,11 @@ __global__ __launch_bounds__(256) void k_distance(const T* __restrict__ X, int n
 // N > 144 kernels) by an ulp: parity there is tolerance-based (1e-5, the
 // north_star bound; tests/test_gpu_parity.py test_distance_high_dim_vs_sklearn),
 // pair indices are exact only where no two distances swap order.
+// Equal rows: the norms' k order is not the Gram products', so n_i need not equal g_ij bit for
+// bit and two equal rows can come back a little above 0 from this kernel (measured: up to
+// 2.7e-6 at D = 96 .. 1050, exactly 0 at D = 4096; k_gram_layer and k_distance, whose norms run
+// in the products' k order, return exactly 0).  The bound is sqrt(E) of tests/dist_ref.py;
+// tests/test_distance_paths.py prints the value per path.
 #ifndef TDA_DM_KC  // build-time A/B knob (tools/): K chunk of k_distance_mfma
 #define TDA_DM_KC 32
 #endif

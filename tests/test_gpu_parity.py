@@ -530,7 +530,7 @@ def test_distance_kernels_agree_with_oracle(gpu, oracle, monkeypatch, dist_kerne
     """The scalar FP64 kernel and the FP64-MFMA Gram kernel (forced both ways
     with TDA_DIST) on ragged N (tile edges) and D (K-chunk edges), f32 and f64
     inputs: within 1e-5 of the oracle, bit-exact on most entries; persistence
-    on top of them bit-exact where the distances are."""
+    (threshold from the row maxima included) bit-exact on the matrix returned."""
     monkeypatch.setenv("TDA_DIST", dist_kernel)
     rng = np.random.default_rng(17)
     for n, d in ((5, 33), (63, 64), (65, 100), (130, 37), (200, 3)):
@@ -543,8 +543,7 @@ def test_distance_kernels_agree_with_oracle(gpu, oracle, monkeypatch, dist_kerne
                 assert np.max(np.abs(got - ref) / np.maximum(1.0, ref)) <= TOL, (n, d)
                 assert np.mean(got == ref) > 0.9, (n, d)
                 assert np.array_equal(res[l].dist, res[l].dist.T) and np.all(np.diag(res[l].dist) == 0)
-                if np.array_equal(got, ref):
-                    assert_same(res[l], oracle.rips_dm(res[l].dist, 1), 1, f"n{n}d{d}")
+                assert_same(res[l], oracle.rips_dm(res[l].dist, 1), 1, f"n{n}d{d}")
 
 
 TWONN_TOL = 1e-4  # relative: the reference runs torch.cdist's f32 Gram form and f32 sums; we use f64 sums
