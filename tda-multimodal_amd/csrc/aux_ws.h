@@ -1,0 +1,104 @@
+// aux_ws.h -- the per-device workspace of the entries beside the persistence pipeline (UMAP, the
+// spectral metrics, greedy landmarks, the two diagram distances), part of rips.hip's translation
+// unit.  Each entry has a stream, buffers and a mutex of its own: no slot's stream is used and
+// nothing is captured into a graph.  The rules these entries share with the pipeline live here:
+// every allocation and free runs under g_capture_mu (never beside a slot's graph capture), a failed
+// growth leaves an empty buffer, and hipFuncSetAttribute runs once per workspace under g_attr_mu.
+// Lock order: an entry's w.mu, then g_capture_mu or g_attr_mu (never both); neither global lock
+// is held across a copy, a launch or a synchronise.
+#pragma once
+
+namespace {
+
+enum AuxEntry { kAuxUmap, kAuxSpectral, kAuxGreedy, kAuxSw, kAuxBn, kAuxEntries };
+
+struct AuxWs {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    hipEvent_t evin = nullptr;      // orders the stream after the caller's (aux_after_caller)
+    hipEvent_t ev[4] = {};          // timing events (aux_events)
+    char* buf = nullptr;            // device
+    size_t cap = 0;
+    char* hout = nullptr;           // pinned and mapped
+    size_t hcap = 0;
+    std::vector<const void*> attr;  // kernels whose dynamic-LDS limit is set (aux_lds_attr)
+    std::mutex mu;                  // held for the whole call
+};
+std::mutex g_aux_mu;
+std::vector<AuxWs*> g_aux_ws[kAuxEntries];
+
+AuxWs& aux_ws(AuxEntry entry, int dev) {
+    std::lock_guard<std::mutex> g(g_aux_mu);
+    for (auto* w : g_aux_ws[entry])
+        if (w->device == dev) return *w;
+    auto* w = new AuxWs();
+    w->device = dev;
+    g_aux_ws[entry].push_back(w);
+    return *w;
+}
+
+// Everything below is called with w.mu held.
+
+// the call's device, the stream (created on the first call) and the first n_events timing events
+int aux_open(AuxWs& w, int n_events = 0) {
+    HIPC(hipSetDevice(w.device));
+    if (!w.stream) HIPC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    for (int i = 0; i < n_events; ++i)
+        if (!w.ev[i]) HIPC(hipEventCreate(&w.ev[i]));
+    return 0;
+}
+
+// device inputs: read after the caller's queued work (NULL = the null stream)
+int aux_after_caller(AuxWs& w, void* caller) {
+    if (!w.evin) HIPC(hipEventCreateWithFlags(&w.evin, hipEventDisableTiming));
+    return order_after_caller(w.stream, w.evin, caller, w.device);
+}
+
+// At least `bytes` of w.buf, then `also()` (a call's further allocations), in one hold of g_capture_mu.
+template <typename Also>
+int aux_reserve(AuxWs& w, size_t bytes, Also&& also) {
+    std::lock_guard<std::mutex> g(g_capture_mu);  // a free synchronises the device: never beside a slot's capture
+    if (w.cap < bytes) {
+        if (w.buf) HIPC(hipFree(w.buf));
+        w.buf = nullptr;
+        w.cap = 0;  // a failed allocation leaves an empty workspace, not a stale size
+        HIPC(hipMalloc(&w.buf, bytes));
+        w.cap = bytes;
+    }
+    return also();
+}
+int aux_reserve(AuxWs& w, size_t bytes) {
+    return w.cap >= bytes ? 0 : aux_reserve(w, bytes, [] { return 0; });  // the lock on growth only
+}
+
+int aux_reserve_pinned(AuxWs& w, size_t bytes) {
+    if (w.hcap >= bytes) return 0;
+    std::lock_guard<std::mutex> g(g_capture_mu);
+    if (w.hout) HIPC(hipHostFree(w.hout));
+    w.hout = nullptr;
+    w.hcap = 0;
+    HIPC(hipHostMalloc((void**)&w.hout, bytes, hipHostMallocMapped));
+    w.hcap = bytes;
+    return 0;
+}
+
+// `fn` may be launched with up to `bytes` of dynamic LDS: set once per workspace (so once per device)
+int aux_lds_attr(AuxWs& w, const void* fn, size_t bytes) {
+    if (std::find(w.attr.begin(), w.attr.end(), fn) != w.attr.end()) return 0;
+    std::lock_guard<std::mutex> g(g_attr_mu);
+    HIPC(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    w.attr.push_back(fn);
+    return 0;
+}
+
+// consecutive 256-byte-aligned offsets into a buffer
+struct Carve {
+    size_t o = 0;
+    size_t take(size_t bytes) {
+        const size_t r = o;
+        o = align_up(o + bytes, 256);
+        return r;
+    }
+};
+
+}  // namespace

@@ -1,11 +1,10 @@
 // bn_host.h -- host side of tda_bottleneck (include/tda_dgm.h), part of rips.hip's
-// translation unit (shares its error state and device checks; dgm_check_layout
-// and dgm_gather are dgm_host.h's).
+// translation unit (shares its error state and device checks; the plan is
+// dgm_plan.h's, the result type and the upload's layout dgm_host.h's).
 //
 // One call, the shape of tda_sliced_wasserstein: drop the non-finite points on
 // the host, sort the pairs into size classes, upload everything in one copy,
-// launch k_bn_pairs once per non-empty class, copy the P distances back.  The
-// workspace, its stream and its mutex are per device and this entry's own.
+// launch k_bn_pairs once per non-empty class, copy the P distances back.
 //
 // Size classes (nm = max(n1, n2) of a pair).  The kernel wants one thread per
 // point of the longer diagram (thread y owns row y of the bitmap), so the
@@ -31,75 +30,21 @@ namespace {
 
 static_assert(kBnMaxN == TDA_BN_MAX_POINTS, "tda_dgm.h and bn_kernels.h disagree");
 
-constexpr int kBnClasses = 3;
-constexpr int kBnClassN[kBnClasses] = {64, 256, kBnMaxN};  // nm at most; also the workgroup size
+constexpr int kBnClassN[kPairClasses] = {64, 256, kBnMaxN};  // nm at most; also the workgroup size
 static_assert(bn_lds_bytes(kBnMaxN, kBnMaxN) <= 64 * 1024, "k_bn_pairs would need hipFuncAttributeMaxDynamicSharedMemorySize");
 
-struct BnWs {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    char* buf = nullptr;
-    size_t cap = 0;
-    std::mutex mu;
-};
-std::mutex g_bn_mu;
-std::vector<BnWs*> g_bn_ws;
-
-BnWs& bn_ws(int dev) {
-    std::lock_guard<std::mutex> g(g_bn_mu);
-    for (auto* w : g_bn_ws)
-        if (w->device == dev) return *w;
-    auto* w = new BnWs();
-    w->device = dev;
-    g_bn_ws.push_back(w);
-    return *w;
-}
-
-struct BnResultImpl {
-    tda_bn_result pub = {};
-    std::unique_ptr<double[]> dist;
-};
-
-struct BnPlan {
-    std::vector<double> pts;     // (total finite, 2)
-    std::vector<int64_t> off;    // [S + 1] into pts
-    std::vector<int32_t> pairs;  // (P, 2)
-    std::vector<int32_t> order;  // [P]: pair ids, class 0 first
-    int64_t cls_cnt[kBnClasses] = {};
-    int cls_n[kBnClasses] = {};  // the largest max(n1, n2) of the class
-    int64_t P = 0;
-};
-
-int bn_plan(const tda_bn_args* a, BnPlan& pl) {
+int bn_plan(const tda_bn_args* a, PairPlan& pl) {
     if (!a) return fail(TDA_E_INVALID, "args is NULL");
     if (a->S < 0) return fail(TDA_E_INVALID, "S must be >= 0");
     if (!a->offsets) return fail(TDA_E_INVALID, "offsets is NULL");
     if (a->reserved != 0) return fail(TDA_E_INVALID, "reserved must be 0");
-    if (int rc = dgm_check_layout(a->points, a->offsets, a->S, a->pairs, a->P, "bottleneck")) return rc;
+    std::string msg;
+    if (int rc = dgm_check_layout(a->points, a->offsets, a->S, a->pairs, a->P, "bottleneck", msg)) return fail(rc, msg);
     const int64_t P = a->pairs ? a->P : a->S * (a->S - 1) / 2;
     if (P > TDA_SW_MAX_WORK) return fail(TDA_E_UNSUPPORTED, "bottleneck: more than 2^27 pairs in one call is not supported (split the pairs)");
-    if (int rc = dgm_gather(a->points, a->offsets, a->S, a->pairs, P, pl.pts, pl.off, pl.pairs)) return rc;
-    pl.P = P;
-    std::vector<uint8_t> cls((size_t)P);
-    for (int64_t p = 0; p < P; ++p) {
-        const int32_t i = pl.pairs[2 * p], j = pl.pairs[2 * p + 1];
-        const int64_t nm = std::max(pl.off[i + 1] - pl.off[i], pl.off[j + 1] - pl.off[j]);
-        if (nm > kBnMaxN) return fail(TDA_E_UNSUPPORTED, "bottleneck: a diagram with more than 512 finite points is not supported");
-        int c = 0;
-        while (nm > kBnClassN[c]) ++c;
-        cls[p] = (uint8_t)c;
-        pl.cls_cnt[c]++;
-        pl.cls_n[c] = std::max(pl.cls_n[c], (int)nm);
-    }
-    pl.order.resize((size_t)P);
-    int64_t at[kBnClasses];
-    int64_t sum = 0;
-    for (int c = 0; c < kBnClasses; ++c) {
-        at[c] = sum;
-        sum += pl.cls_cnt[c];
-    }
-    for (int64_t p = 0; p < P; ++p) pl.order[at[cls[p]]++] = (int32_t)p;
+    if (int rc = dgm_gather(a->points, a->offsets, a->S, a->pairs, P, pl, msg)) return fail(rc, msg);
+    if (int rc = dgm_classify(pl, PairSize::kMax, kBnClassN, "bottleneck: a diagram with more than 512 finite points is not supported", msg))
+        return fail(rc, msg);
     return 0;
 }
 
@@ -108,70 +53,46 @@ int bn_plan(const tda_bn_args* a, BnPlan& pl) {
 extern "C" int tda_bottleneck(const tda_bn_args* a, tda_bn_result** out) {
     if (!out) return fail(TDA_E_INVALID, "out is NULL");
     *out = nullptr;
-    BnPlan pl;
+    PairPlan pl;
     if (int rc = bn_plan(a, pl)) return rc;
     if (!tda_device_ok(a->device)) return fail(TDA_E_NODEVICE, "no gfx950 device at ordinal " + std::to_string(a->device));
     const size_t P = (size_t)pl.P;
-    std::unique_ptr<BnResultImpl> R(new BnResultImpl());
-    R->dist.reset(new double[std::max<size_t>(P, 1)]);
-    R->pub.P = pl.P;
-    R->pub.dist = R->dist.get();
+    std::unique_ptr<DgmResultImpl<tda_bn_result>> R(new DgmResultImpl<tda_bn_result>(pl.P));
     if (P == 0) {  // nothing to launch
         *out = &R.release()->pub;
         return 0;
     }
 
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o = align_up(o + bytes, 256);
-        return r;
-    };
-    const size_t o_pts = take(pl.pts.size() * 8), o_off = take(pl.off.size() * 8), o_pairs = take(pl.pairs.size() * 4);
-    const size_t o_order = take(pl.order.size() * 4);
-    const size_t up_bytes = o;  // the uploaded part
-    const size_t o_dist = take(P * 8);
+    Carve cv;
+    const PlanAt at(pl, cv);
+    const size_t up_bytes = cv.o;  // the uploaded part
+    const size_t o_dist = cv.take(P * 8);
     std::vector<char> up(up_bytes);
-    if (!pl.pts.empty()) std::memcpy(up.data() + o_pts, pl.pts.data(), pl.pts.size() * 8);
-    std::memcpy(up.data() + o_off, pl.off.data(), pl.off.size() * 8);
-    std::memcpy(up.data() + o_pairs, pl.pairs.data(), pl.pairs.size() * 4);
-    std::memcpy(up.data() + o_order, pl.order.data(), pl.order.size() * 4);
+    at.pack(pl, up.data());
 
-    HIPC(hipSetDevice(a->device));
-    BnWs& w = bn_ws(a->device);
+    AuxWs& w = aux_ws(kAuxBn, a->device);
     std::lock_guard<std::mutex> guard(w.mu);
-    if (!w.stream) HIPC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    if (!w.ev0) {
-        HIPC(hipEventCreate(&w.ev0));
-        HIPC(hipEventCreate(&w.ev1));
-    }
-    if (w.cap < o) {
-        std::lock_guard<std::mutex> g(g_capture_mu);  // allocations never beside a slot's graph capture
-        if (w.buf) HIPC(hipFree(w.buf));
-        w.buf = nullptr;
-        w.cap = 0;
-        HIPC(hipMalloc(&w.buf, o));
-        w.cap = o;
-    }
+    if (int rc = aux_open(w, 2)) return rc;
+    if (int rc = aux_reserve(w, cv.o)) return rc;
     hipStream_t s = w.stream;
     double* dist = (double*)(w.buf + o_dist);
-    HIPC(hipEventRecord(w.ev0, s));
+    HIPC(hipEventRecord(w.ev[0], s));
     HIPC(hipMemcpyAsync(w.buf, up.data(), up_bytes, hipMemcpyHostToDevice, s));
     int64_t first = 0;
-    for (int c = 0; c < kBnClasses; ++c) {
+    for (int c = 0; c < kPairClasses; ++c) {
         const int64_t cnt = pl.cls_cnt[c];
         if (!cnt) continue;
         hipLaunchKernelGGL(k_bn_pairs, dim3((unsigned)cnt), dim3(kBnClassN[c]), bn_lds_bytes(pl.cls_n[c], pl.cls_n[c]), s,
-                           (const double*)(w.buf + o_pts), (const int64_t*)(w.buf + o_off), (const int32_t*)(w.buf + o_pairs),
-                           (const int32_t*)(w.buf + o_order) + first, dist);
+                           (const double*)(w.buf + at.pts), (const int64_t*)(w.buf + at.off), (const int32_t*)(w.buf + at.pairs),
+                           (const int32_t*)(w.buf + at.order) + first, dist);
         HIPC(hipGetLastError());
         first += cnt;
     }
     HIPC(hipMemcpyAsync(R->dist.get(), dist, P * 8, hipMemcpyDeviceToHost, s));
-    HIPC(hipEventRecord(w.ev1, s));
+    HIPC(hipEventRecord(w.ev[1], s));
     HIPC(hipStreamSynchronize(s));
     float ms = 0.0f;
-    HIPC(hipEventElapsedTime(&ms, w.ev0, w.ev1));
+    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
     // no cost is a NaN (the coordinates are finite), so a NaN is the kernel's word for "a loop bound was hit"
     for (size_t p = 0; p < P; ++p)
         if (std::isnan(R->dist[p]))
@@ -181,7 +102,4 @@ extern "C" int tda_bottleneck(const tda_bn_args* a, tda_bn_result** out) {
     return 0;
 }
 
-extern "C" void tda_bn_free(tda_bn_result* r) {
-    if (!r) return;
-    delete reinterpret_cast<BnResultImpl*>(r);  // pub is the first member
-}
+extern "C" void tda_bn_free(tda_bn_result* r) { dgm_free(r); }

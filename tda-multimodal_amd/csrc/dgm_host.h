@@ -3,9 +3,8 @@
 //
 // One call: drop the non-finite points on the host, sort the pairs into three
 // size classes, upload everything in one copy, launch k_sw_pairs once per
-// non-empty class and k_sw_sum once, copy the P distances back.  The workspace,
-// its stream and its mutex are per device and this entry's own (no slot's
-// stream is used, nothing is captured into a graph).
+// non-empty class and k_sw_sum once, copy the P distances back (the plan:
+// dgm_plan.h; the workspace: aux_ws.h).
 //
 // Size classes (npow = next_pow2(n1 + n2) of a pair): a launch has one
 // workgroup size and one dynamic-LDS size, and both should fit the pair.
@@ -22,6 +21,7 @@
 #pragma once
 #include "../../include/tda_dgm.h"
 #include "dgm_kernels.h"
+#include "dgm_plan.h"
 
 namespace {
 
@@ -32,115 +32,50 @@ struct SwClass {
 };
 constexpr SwClass kSwClasses[3] = {{128, 64, 8}, {1024, 256, 1}, {kSwMaxN, 1024, 1}};
 
-struct SwWs {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    char* buf = nullptr;
-    size_t cap = 0;
-    bool attr = false;
-    std::mutex mu;
-};
-std::mutex g_sw_mu;
-std::vector<SwWs*> g_sw_ws;
-
-SwWs& sw_ws(int dev) {
-    std::lock_guard<std::mutex> g(g_sw_mu);
-    for (auto* w : g_sw_ws)
-        if (w->device == dev) return *w;
-    auto* w = new SwWs();
-    w->device = dev;
-    g_sw_ws.push_back(w);
-    return *w;
-}
-
-struct SwResultImpl {
-    tda_sw_result pub = {};
+// one result type for both distances: the public structs have the same layout but are distinct types
+template <typename Pub>
+struct DgmResultImpl {
+    Pub pub = {};
     std::unique_ptr<double[]> dist;
+    explicit DgmResultImpl(int64_t P) : dist(new double[std::max<int64_t>(P, 1)]) {
+        pub.P = P;
+        pub.dist = dist.get();
+    }
 };
-
-// what the device reads, laid out on the host: one upload
-struct SwPlan {
-    std::vector<double> pts;     // (total finite, 2)
-    std::vector<int64_t> off;    // [S + 1] into pts
-    std::vector<int32_t> pairs;  // (P, 2)
-    std::vector<int32_t> order;  // [P]: pair ids, class 0 first
-    int64_t cls_cnt[3] = {0, 0, 0};
-    int cls_n[3] = {0, 0, 0};  // the largest n1 + n2 of the class
-    int64_t P = 0;
-};
-
-// The layout checks every entry of tda_dgm.h shares, in the order tda_sliced_wasserstein has always made them
-// (S >= 0 and offsets != NULL are checked by the caller first, with its own checks in between).
-int dgm_check_layout(const double* points, const int64_t* offsets, int64_t S, const int32_t* pairs, int64_t P, const char* what) {
-    if (offsets[0] != 0) return fail(TDA_E_INVALID, "offsets[0] must be 0");
-    for (int64_t s = 0; s < S; ++s)
-        if (offsets[s + 1] < offsets[s]) return fail(TDA_E_INVALID, "offsets must be non-decreasing");
-    if (offsets[S] > 0 && !points) return fail(TDA_E_INVALID, "points is NULL");
-    if (pairs && P < 0) return fail(TDA_E_INVALID, "P must be >= 0");
-    if (S > TDA_SW_MAX_WORK) return fail(TDA_E_UNSUPPORTED, std::string(what) + ": too many diagrams in one call");
-    return 0;
+template <typename Pub>
+void dgm_free(Pub* r) {
+    delete reinterpret_cast<DgmResultImpl<Pub>*>(r);  // pub is the first member; NULL is a no-op
 }
 
-// The part of a call's plan that every distance of tda_dgm.h shares (bn_host.h uses it too): the finite
-// points of the S diagrams (the essential classes dropped) with their row boundaries, and the P pairs,
-// copied and index-checked or, for pairs == NULL, every i < j in row-major order.  offsets is valid.
-int dgm_gather(const double* points, const int64_t* offsets, int64_t S, const int32_t* pairs, int64_t P, std::vector<double>& pts,
-               std::vector<int64_t>& off, std::vector<int32_t>& prs) {
-    off.assign((size_t)S + 1, 0);
-    pts.reserve((size_t)offsets[S] * 2);
-    for (int64_t s = 0; s < S; ++s) {
-        for (int64_t r = offsets[s]; r < offsets[s + 1]; ++r) {
-            const double b = points[2 * r], d = points[2 * r + 1];
-            if (!std::isfinite(b) || !std::isfinite(d)) continue;  // the essential classes
-            pts.push_back(b);
-            pts.push_back(d);
-        }
-        off[s + 1] = (int64_t)(pts.size() / 2);
+// the plan's four arrays at the head of a call's buffer (carved first, in this order), packed for one upload
+struct PlanAt {
+    size_t pts, off, pairs, order;
+    PlanAt(const PairPlan& pl, Carve& cv)
+        : pts(cv.take(pl.pts.size() * 8)), off(cv.take(pl.off.size() * 8)), pairs(cv.take(pl.pairs.size() * 4)),
+          order(cv.take(pl.order.size() * 4)) {}
+    void pack(const PairPlan& pl, char* up) const {
+        if (!pl.pts.empty()) std::memcpy(up + pts, pl.pts.data(), pl.pts.size() * 8);
+        std::memcpy(up + off, pl.off.data(), pl.off.size() * 8);
+        std::memcpy(up + pairs, pl.pairs.data(), pl.pairs.size() * 4);
+        std::memcpy(up + order, pl.order.data(), pl.order.size() * 4);
     }
-    prs.resize((size_t)P * 2);
-    if (pairs) {
-        for (int64_t q = 0; q < 2 * P; ++q) {
-            if (pairs[q] < 0 || pairs[q] >= S) return fail(TDA_E_INVALID, "pairs holds an index outside [0, S)");
-            prs[q] = pairs[q];
-        }
-    } else {
-        size_t q = 0;
-        for (int32_t i = 0; i < S; ++i)
-            for (int32_t j = i + 1; j < S; ++j) {
-                prs[q++] = i;
-                prs[q++] = j;
-            }
-    }
-    return 0;
-}
+};
 
-int sw_plan(const tda_sw_args* a, SwPlan& pl) {
+int sw_plan(const tda_sw_args* a, PairPlan& pl) {
     if (!a) return fail(TDA_E_INVALID, "args is NULL");
     if (a->S < 0) return fail(TDA_E_INVALID, "S must be >= 0");
     if (!a->offsets) return fail(TDA_E_INVALID, "offsets is NULL");
     if (a->M < 1) return fail(TDA_E_INVALID, "M must be >= 1");
     if (a->M > kSwMaxM) return fail(TDA_E_UNSUPPORTED, "sliced Wasserstein: M > 1024 directions is not supported");
-    if (int rc = dgm_check_layout(a->points, a->offsets, a->S, a->pairs, a->P, "sliced Wasserstein")) return rc;
+    std::string msg;
+    if (int rc = dgm_check_layout(a->points, a->offsets, a->S, a->pairs, a->P, "sliced Wasserstein", msg)) return fail(rc, msg);
     const int64_t P = a->pairs ? a->P : a->S * (a->S - 1) / 2;
     if (P > TDA_SW_MAX_WORK || P * a->M > TDA_SW_MAX_WORK) return fail(TDA_E_UNSUPPORTED, "sliced Wasserstein: P * M > 2^27 in one call is not supported (split the pairs)");
-
-    if (int rc = dgm_gather(a->points, a->offsets, a->S, a->pairs, P, pl.pts, pl.off, pl.pairs)) return rc;
-    pl.P = P;
-    std::vector<uint8_t> cls((size_t)P);
-    for (int64_t p = 0; p < P; ++p) {
-        const int32_t i = pl.pairs[2 * p], j = pl.pairs[2 * p + 1];
-        const int64_t n = (pl.off[i + 1] - pl.off[i]) + (pl.off[j + 1] - pl.off[j]);
-        if (n > kSwMaxN)
-            return fail(TDA_E_UNSUPPORTED, "sliced Wasserstein: a pair of diagrams with more than 4096 finite points together is not supported");
-        const int c = n <= kSwClasses[0].npow_max ? 0 : n <= kSwClasses[1].npow_max ? 1 : 2;
-        cls[p] = (uint8_t)c;
-        pl.cls_cnt[c]++;
-        pl.cls_n[c] = std::max(pl.cls_n[c], (int)n);
-    }
-    pl.order.resize((size_t)P);
-    int64_t at[3] = {0, pl.cls_cnt[0], pl.cls_cnt[0] + pl.cls_cnt[1]};
-    for (int64_t p = 0; p < P; ++p) pl.order[at[cls[p]]++] = (int32_t)p;
+    if (int rc = dgm_gather(a->points, a->offsets, a->S, a->pairs, P, pl, msg)) return fail(rc, msg);
+    const int limits[kPairClasses] = {kSwClasses[0].npow_max, kSwClasses[1].npow_max, kSwClasses[2].npow_max};
+    if (int rc = dgm_classify(pl, PairSize::kSum, limits,
+                              "sliced Wasserstein: a pair of diagrams with more than 4096 finite points together is not supported", msg))
+        return fail(rc, msg);
     return 0;
 }
 
@@ -149,14 +84,11 @@ int sw_plan(const tda_sw_args* a, SwPlan& pl) {
 extern "C" int tda_sliced_wasserstein(const tda_sw_args* a, tda_sw_result** out) {
     if (!out) return fail(TDA_E_INVALID, "out is NULL");
     *out = nullptr;
-    SwPlan pl;
+    PairPlan pl;
     if (int rc = sw_plan(a, pl)) return rc;
     if (!tda_device_ok(a->device)) return fail(TDA_E_NODEVICE, "no gfx950 device at ordinal " + std::to_string(a->device));
     const size_t P = (size_t)pl.P, M = (size_t)a->M;
-    std::unique_ptr<SwResultImpl> R(new SwResultImpl());
-    R->dist.reset(new double[std::max<size_t>(P, 1)]);
-    R->pub.P = pl.P;
-    R->pub.dist = R->dist.get();
+    std::unique_ptr<DgmResultImpl<tda_sw_result>> R(new DgmResultImpl<tda_sw_result>(pl.P));
     if (P == 0) {  // nothing to launch
         *out = &R.release()->pub;
         return 0;
@@ -171,75 +103,49 @@ extern "C" int tda_sliced_wasserstein(const tda_sw_args* a, tda_sw_result** out)
         dirs[2 * i + 1] = std::sin(th);
     }
 
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o = align_up(o + bytes, 256);
-        return r;
-    };
-    const size_t o_pts = take(pl.pts.size() * 8), o_off = take(pl.off.size() * 8), o_pairs = take(pl.pairs.size() * 4);
-    const size_t o_order = take(pl.order.size() * 4), o_dirs = take(dirs.size() * 8);
-    const size_t up_bytes = o;  // the uploaded part
-    const size_t o_part = take(P * M * 8), o_dist = take(P * 8);
+    Carve cv;
+    const PlanAt at(pl, cv);
+    const size_t o_dirs = cv.take(dirs.size() * 8);
+    const size_t up_bytes = cv.o;  // the uploaded part
+    const size_t o_part = cv.take(P * M * 8), o_dist = cv.take(P * 8);
     std::vector<char> up(up_bytes);
-    if (!pl.pts.empty()) std::memcpy(up.data() + o_pts, pl.pts.data(), pl.pts.size() * 8);
-    std::memcpy(up.data() + o_off, pl.off.data(), pl.off.size() * 8);
-    std::memcpy(up.data() + o_pairs, pl.pairs.data(), pl.pairs.size() * 4);
-    std::memcpy(up.data() + o_order, pl.order.data(), pl.order.size() * 4);
+    at.pack(pl, up.data());
     std::memcpy(up.data() + o_dirs, dirs.data(), dirs.size() * 8);
 
-    HIPC(hipSetDevice(a->device));
-    SwWs& w = sw_ws(a->device);
+    AuxWs& w = aux_ws(kAuxSw, a->device);
     std::lock_guard<std::mutex> guard(w.mu);
-    if (!w.stream) HIPC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    if (!w.ev0) {
-        HIPC(hipEventCreate(&w.ev0));
-        HIPC(hipEventCreate(&w.ev1));
-    }
-    if (!w.attr) {
-        HIPC(hipFuncSetAttribute((const void*)k_sw_pairs, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sw_lds_bytes(kSwMaxN, kSwMaxN)));
-        w.attr = true;
-    }
-    if (w.cap < o) {
-        std::lock_guard<std::mutex> g(g_capture_mu);  // allocations never beside a slot's graph capture
-        if (w.buf) HIPC(hipFree(w.buf));
-        w.buf = nullptr;
-        w.cap = 0;
-        HIPC(hipMalloc(&w.buf, o));
-        w.cap = o;
-    }
+    if (int rc = aux_open(w, 2)) return rc;
+    if (int rc = aux_lds_attr(w, (const void*)k_sw_pairs, sw_lds_bytes(kSwMaxN, kSwMaxN))) return rc;
+    if (int rc = aux_reserve(w, cv.o)) return rc;
     hipStream_t s = w.stream;
     double* part = (double*)(w.buf + o_part);
     double* dist = (double*)(w.buf + o_dist);
-    HIPC(hipEventRecord(w.ev0, s));
+    HIPC(hipEventRecord(w.ev[0], s));
     HIPC(hipMemcpyAsync(w.buf, up.data(), up_bytes, hipMemcpyHostToDevice, s));
     int64_t first = 0;
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < kPairClasses; ++c) {
         const int64_t cnt = pl.cls_cnt[c];
         if (!cnt) continue;
         const SwClass& k = kSwClasses[c];
         const int n = pl.cls_n[c];
         const size_t lds = sw_lds_bytes(n, (int)next_pow2((uint64_t)std::max(n, 1)));
         const unsigned chunks = (unsigned)((a->M + k.dirs_per_wg - 1) / k.dirs_per_wg);
-        hipLaunchKernelGGL(k_sw_pairs, dim3((unsigned)cnt, chunks), dim3(k.threads), lds, s, (const double*)(w.buf + o_pts),
-                           (const int64_t*)(w.buf + o_off), (const int32_t*)(w.buf + o_pairs),
-                           (const int32_t*)(w.buf + o_order) + first, (const double*)(w.buf + o_dirs), (int)a->M, k.dirs_per_wg, part);
+        hipLaunchKernelGGL(k_sw_pairs, dim3((unsigned)cnt, chunks), dim3(k.threads), lds, s, (const double*)(w.buf + at.pts),
+                           (const int64_t*)(w.buf + at.off), (const int32_t*)(w.buf + at.pairs),
+                           (const int32_t*)(w.buf + at.order) + first, (const double*)(w.buf + o_dirs), (int)a->M, k.dirs_per_wg, part);
         HIPC(hipGetLastError());
         first += cnt;
     }
     hipLaunchKernelGGL(k_sw_sum, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, (const double*)part, (int64_t)P, (int)a->M, dist);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(R->dist.get(), dist, P * 8, hipMemcpyDeviceToHost, s));
-    HIPC(hipEventRecord(w.ev1, s));
+    HIPC(hipEventRecord(w.ev[1], s));
     HIPC(hipStreamSynchronize(s));
     float ms = 0.0f;
-    HIPC(hipEventElapsedTime(&ms, w.ev0, w.ev1));
+    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
     R->pub.device_ms = ms;
     *out = &R.release()->pub;
     return 0;
 }
 
-extern "C" void tda_sw_free(tda_sw_result* r) {
-    if (!r) return;
-    delete reinterpret_cast<SwResultImpl*>(r);  // pub is the first member
-}
+extern "C" void tda_sw_free(tda_sw_result* r) { dgm_free(r); }

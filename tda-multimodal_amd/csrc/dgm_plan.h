@@ -1,0 +1,104 @@
+// dgm_plan.h -- the host plan of a call of include/tda_dgm.h (tda_sliced_wasserstein, tda_bottleneck):
+// the layout checks, the finite points and the pair list, and the pairs sorted into size classes.
+// Plain C++, no HIP: a function returns an error code and leaves its message in `msg`
+// (tests/dgm_plan_main.cpp runs every case with a host compiler alone).
+#pragma once
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/tda_dgm.h"
+
+namespace tda {
+
+constexpr int kPairClasses = 3;
+
+// what the device reads, laid out on the host: one upload
+struct PairPlan {
+    std::vector<double> pts;     // (total finite, 2)
+    std::vector<int64_t> off;    // [S + 1] into pts
+    std::vector<int32_t> pairs;  // (P, 2)
+    std::vector<int32_t> order;  // [P]: pair ids, class 0 first, ascending within a class
+    int64_t cls_cnt[kPairClasses] = {};
+    int cls_n[kPairClasses] = {};  // the largest size of the class
+    int64_t P = 0;
+};
+
+// The layout checks every entry of tda_dgm.h shares, in the order tda_sliced_wasserstein has always made them
+// (S >= 0 and offsets != NULL are checked by the caller first, with its own checks in between).
+inline int dgm_check_layout(const double* points, const int64_t* offsets, int64_t S, const int32_t* pairs, int64_t P, const char* what,
+                            std::string& msg) {
+    auto bad = [&](int code, const std::string& m) { return msg = m, code; };
+    if (offsets[0] != 0) return bad(TDA_E_INVALID, "offsets[0] must be 0");
+    for (int64_t s = 0; s < S; ++s)
+        if (offsets[s + 1] < offsets[s]) return bad(TDA_E_INVALID, "offsets must be non-decreasing");
+    if (offsets[S] > 0 && !points) return bad(TDA_E_INVALID, "points is NULL");
+    if (pairs && P < 0) return bad(TDA_E_INVALID, "P must be >= 0");
+    if (S > TDA_SW_MAX_WORK) return bad(TDA_E_UNSUPPORTED, std::string(what) + ": too many diagrams in one call");
+    return 0;
+}
+
+// pl.pts / off: the finite points of the S diagrams (the essential classes dropped) with their row
+// boundaries; pl.pairs / P: the P pairs, copied and index-checked or, for pairs == NULL, every i < j in
+// row-major order.  offsets is valid (dgm_check_layout).
+inline int dgm_gather(const double* points, const int64_t* offsets, int64_t S, const int32_t* pairs, int64_t P, PairPlan& pl,
+                      std::string& msg) {
+    pl.P = P;
+    pl.off.assign((size_t)S + 1, 0);
+    pl.pts.reserve((size_t)offsets[S] * 2);
+    for (int64_t s = 0; s < S; ++s) {
+        for (int64_t r = offsets[s]; r < offsets[s + 1]; ++r) {
+            const double b = points[2 * r], d = points[2 * r + 1];
+            if (!std::isfinite(b) || !std::isfinite(d)) continue;  // the essential classes
+            pl.pts.push_back(b);
+            pl.pts.push_back(d);
+        }
+        pl.off[s + 1] = (int64_t)(pl.pts.size() / 2);
+    }
+    pl.pairs.resize((size_t)P * 2);
+    if (pairs) {
+        for (int64_t q = 0; q < 2 * P; ++q) {
+            if (pairs[q] < 0 || pairs[q] >= S) return msg = "pairs holds an index outside [0, S)", TDA_E_INVALID;
+            pl.pairs[q] = pairs[q];
+        }
+    } else {
+        size_t q = 0;
+        for (int32_t i = 0; i < S; ++i)
+            for (int32_t j = i + 1; j < S; ++j) {
+                pl.pairs[q++] = i;
+                pl.pairs[q++] = j;
+            }
+    }
+    return 0;
+}
+
+enum class PairSize { kSum, kMax };  // a pair's size: n1 + n2 or max(n1, n2) finite points
+
+// Sorts the gathered pairs into classes: class c holds the pairs of size <= limits[c] (ascending;
+// the last one is the limit of a call: a larger pair is TDA_E_UNSUPPORTED with `too_large`).
+inline int dgm_classify(PairPlan& pl, PairSize measure, const int (&limits)[kPairClasses], const char* too_large, std::string& msg) {
+    std::vector<uint8_t> cls((size_t)pl.P);
+    for (int64_t p = 0; p < pl.P; ++p) {
+        const int32_t i = pl.pairs[2 * p], j = pl.pairs[2 * p + 1];
+        const int64_t n1 = pl.off[i + 1] - pl.off[i], n2 = pl.off[j + 1] - pl.off[j];
+        const int64_t n = measure == PairSize::kSum ? n1 + n2 : std::max(n1, n2);
+        if (n > limits[kPairClasses - 1]) return msg = too_large, TDA_E_UNSUPPORTED;
+        int c = 0;
+        while (n > limits[c]) ++c;
+        cls[p] = (uint8_t)c;
+        pl.cls_cnt[c]++;
+        pl.cls_n[c] = std::max(pl.cls_n[c], (int)n);
+    }
+    pl.order.resize((size_t)pl.P);
+    int64_t at[kPairClasses], sum = 0;
+    for (int c = 0; c < kPairClasses; ++c) {
+        at[c] = sum;
+        sum += pl.cls_cnt[c];
+    }
+    for (int64_t p = 0; p < pl.P; ++p) pl.order[at[cls[p]]++] = (int32_t)p;
+    return 0;
+}
+
+}  // namespace tda

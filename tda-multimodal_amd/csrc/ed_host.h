@@ -6,29 +6,6 @@
 
 namespace {
 
-struct EdWs {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t evin = nullptr;
-    char* buf = nullptr;
-    size_t cap = 0;
-    float* hout = nullptr;  // pinned result
-    size_t hcap = 0;
-    std::mutex mu;
-};
-std::mutex g_ed_mu;
-std::vector<EdWs*> g_ed_ws;
-
-EdWs& ed_ws(int dev) {
-    std::lock_guard<std::mutex> g(g_ed_mu);
-    for (auto* w : g_ed_ws)
-        if (w->device == dev) return *w;
-    auto* w = new EdWs();
-    w->device = dev;
-    g_ed_ws.push_back(w);
-    return *w;
-}
-
 // One call's work, validated: B matrices of N x D.  src_items > 0: the B
 // matrices are the windows of src_items items of src_rows rows each, of which
 // only the first keep_rows are used (a remainder is dropped), so the kept rows
@@ -54,37 +31,19 @@ template <typename Epi>
 int ed_run(const EdJob& j, const Epi& epi, int64_t per_item, float* out) {
     const int64_t B = j.B, N = j.N, D = j.D, m = std::min(N, D);
     if (!tda_device_ok(j.device)) return fail(TDA_E_NODEVICE, "no gfx950 device at ordinal " + std::to_string(j.device));
-    HIPC(hipSetDevice(j.device));
-    EdWs& w = ed_ws(j.device);
+    AuxWs& w = aux_ws(kAuxSpectral, j.device);
     std::lock_guard<std::mutex> guard(w.mu);
-    if (!w.stream) HIPC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    if (int rc = aux_open(w)) return rc;
     hipStream_t s = w.stream;
-    if (j.x_on_device) {  // device inputs: read after the caller's queued work (NULL = the null stream)
-        if (!w.evin) HIPC(hipEventCreateWithFlags(&w.evin, hipEventDisableTiming));
-        if (int rc = order_after_caller(s, w.evin, j.stream, j.device)) return rc;
-    }
+    if (j.x_on_device)
+        if (int rc = aux_after_caller(w, j.stream)) return rc;
     const size_t esz = j.dtype == TDA_F64 ? 8 : 4;
     const bool stage = j.src_items > 0;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o = align_up(o + bytes, 256);
-        return r;
-    };
-    const size_t o_x = take(j.x_on_device && !stage ? 0 : (size_t)B * N * D * esz), o_g = take((size_t)B * m * m * 8);
-    if (w.cap < o) {
-        if (w.buf) HIPC(hipFree(w.buf));
-        w.buf = nullptr;
-        HIPC(hipMalloc(&w.buf, o));
-        w.cap = o;
-    }
+    Carve cv;
+    const size_t o_x = cv.take(j.x_on_device && !stage ? 0 : (size_t)B * N * D * esz), o_g = cv.take((size_t)B * m * m * 8);
+    if (int rc = aux_reserve(w, cv.o)) return rc;
     const size_t n_out = (size_t)(B * per_item);
-    if (w.hcap < n_out) {
-        if (w.hout) HIPC(hipHostFree(w.hout));
-        w.hout = nullptr;
-        HIPC(hipHostMalloc((void**)&w.hout, sizeof(float) * n_out, hipHostMallocMapped));
-        w.hcap = n_out;
-    }
+    if (int rc = aux_reserve_pinned(w, sizeof(float) * n_out)) return rc;  // the result
     const void* x = j.x;
     if (stage) {  // the kept rows of every item, packed: they then are (B, N, D)
         const size_t width = (size_t)j.keep_rows * D * esz;
@@ -120,7 +79,7 @@ int ed_run(const EdJob& j, const Epi& epi, int64_t per_item, float* out) {
     float* dout = nullptr;
     HIPC(hipHostGetDevicePointer((void**)&dout, w.hout, 0));
     if (m <= kEdLdsMaxM) {
-        HIPC(hipFuncSetAttribute((const void*)k_ed_jacobi<true, Epi>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * kEdLdsMaxM * kEdLdsMaxM));
+        if (int rc = aux_lds_attr(w, (const void*)k_ed_jacobi<true, Epi>, 8 * kEdLdsMaxM * kEdLdsMaxM)) return rc;
         hipLaunchKernelGGL((k_ed_jacobi<true, Epi>), dim3((unsigned)B), dim3(kEdT), (size_t)8 * m * m, s, G, (int)m, epi, dout);
     } else {
         hipLaunchKernelGGL((k_ed_jacobi<false, Epi>), dim3((unsigned)B), dim3(kEdT), 0, s, G, (int)m, epi, dout);

@@ -14,27 +14,6 @@
 
 namespace {
 
-struct GreedyWs {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t evin = nullptr, ev0 = nullptr, ev1 = nullptr, evk0 = nullptr, evk1 = nullptr;
-    char* buf = nullptr;
-    size_t cap = 0;
-    std::mutex mu;
-};
-std::mutex g_greedy_mu;
-std::vector<GreedyWs*> g_greedy_ws;
-
-GreedyWs& greedy_ws(int dev) {
-    std::lock_guard<std::mutex> g(g_greedy_mu);
-    for (auto* w : g_greedy_ws)
-        if (w->device == dev) return *w;
-    auto* w = new GreedyWs();
-    w->device = dev;
-    g_greedy_ws.push_back(w);
-    return *w;
-}
-
 struct GreedyResultImpl {
     tda_greedy_result pub = {};
     std::unique_ptr<int64_t[]> idx;
@@ -83,17 +62,11 @@ extern "C" int tda_greedy_perm(const tda_greedy_args* a, tda_greedy_result** out
     const DistSel sel = dist_select(N, a->D, a->dtype, is_dist);
     const size_t sp = (size_t)sel.dsplit;
 
-    HIPC(hipSetDevice(a->device));
-    GreedyWs& w = greedy_ws(a->device);
+    AuxWs& w = aux_ws(kAuxGreedy, a->device);
     std::lock_guard<std::mutex> guard(w.mu);
-    if (!w.stream) HIPC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    if (!w.ev0) {
-        HIPC(hipEventCreate(&w.ev0));
-        HIPC(hipEventCreate(&w.ev1));
-        HIPC(hipEventCreate(&w.evk0));
-        HIPC(hipEventCreate(&w.evk1));
-    }
+    if (int rc = aux_open(w, 4)) return rc;
     hipStream_t s = w.stream;
+    const hipEvent_t ev0 = w.ev[0], ev1 = w.ev[1], evk0 = w.ev[2], evk1 = w.ev[3];  // the call; k_greedy_perm of a chunk
 
     // chunk of layers: the largest whose workspace stays within the cap (one layer at least)
     size_t per_layer = 0;
@@ -105,42 +78,29 @@ extern "C" int tda_greedy_perm(const tda_greedy_args* a, tda_greedy_result** out
     add(sel.partials() ? sp * N * 8 : 0);
     add(want_dp ? k * N * 4 : 0);
     const size_t Lc = std::min<size_t>(std::min<size_t>(L, 65535), std::max<size_t>(1, (size_t)TDA_GREEDY_WS_BYTES / per_layer));
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o = align_up(o + bytes, 256);
-        return r;
-    };
-    const size_t o_idx = take(L * k * 8), o_lam = take(L * k * 4);
-    const size_t o_x = take(host_in ? Lc * x_layer : 0), o_dm = take(Lc * N * N * 4), o_rm = take(Lc * N * 4);
-    const size_t o_gp = take(sel.partials() ? Lc * sp * N * N * 8 : 0), o_np = take(sel.partials() ? Lc * sp * N * 8 : 0);
-    const size_t o_dp = take(want_dp ? Lc * k * N * 4 : 0);
+    Carve cv;
+    const size_t o_idx = cv.take(L * k * 8), o_lam = cv.take(L * k * 4);
+    const size_t o_x = cv.take(host_in ? Lc * x_layer : 0), o_dm = cv.take(Lc * N * N * 4), o_rm = cv.take(Lc * N * 4);
+    const size_t o_gp = cv.take(sel.partials() ? Lc * sp * N * N * 8 : 0), o_np = cv.take(sel.partials() ? Lc * sp * N * 8 : 0);
+    const size_t o_dp = cv.take(want_dp ? Lc * k * N * 4 : 0);
 
     std::unique_ptr<GreedyResultImpl> R(new GreedyResultImpl());
     R->idx.reset(new int64_t[L * k]);
     R->lam.reset(new float[L * k]);
     if (want_dp) R->dperm.reset(new float[L * k * N]);
-    {
-        std::lock_guard<std::mutex> g(g_capture_mu);  // allocations never beside a slot's graph capture
-        if (w.cap < o) {
-            if (w.buf) HIPC(hipFree(w.buf));
-            w.buf = nullptr;
-            w.cap = 0;
-            HIPC(hipMalloc(&w.buf, o));
-            w.cap = o;
-        }
+    const auto alloc_sub = [&]() -> int {  // the result's own buffer, in the same hold of g_capture_mu
         HIPC(hipMalloc((void**)&R->sub_dev, L * k * k * 4));
-    }
-    if (a->x_on_device) {  // device inputs: read after the caller's queued work (NULL = the null stream)
-        if (!w.evin) HIPC(hipEventCreateWithFlags(&w.evin, hipEventDisableTiming));
-        if (int rc = order_after_caller(s, w.evin, a->stream, a->device)) return rc;
-    }
+        return 0;
+    };
+    if (int rc = aux_reserve(w, cv.o, alloc_sub)) return rc;
+    if (a->x_on_device)
+        if (int rc = aux_after_caller(w, a->stream)) return rc;
     int64_t* d_idx = (int64_t*)(w.buf + o_idx);
     float* d_lam = (float*)(w.buf + o_lam);
     float* dm = (float*)(w.buf + o_dm);
     float* d_dp = want_dp ? (float*)(w.buf + o_dp) : nullptr;
     double select_ms = 0.0;
-    HIPC(hipEventRecord(w.ev0, s));
+    HIPC(hipEventRecord(ev0, s));
     for (size_t l0 = 0; l0 < L; l0 += Lc) {
         const size_t lc = std::min(Lc, L - l0);
         const void* x = (const char*)a->x + l0 * x_layer;
@@ -161,10 +121,10 @@ extern "C" int tda_greedy_perm(const tda_greedy_args* a, tda_greedy_result** out
                 hipLaunchKernelGGL(k_square_dist<float>, dim3(gx, (unsigned)lc), dim3(256), 0, s, (const float*)x, n, dm);
         }
         HIPC(hipGetLastError());
-        HIPC(hipEventRecord(w.evk0, s));
+        HIPC(hipEventRecord(evk0, s));
         launch_greedy_perm(s, dm, (int)lc, n, (int)k, d_idx + l0 * k, d_lam + l0 * k);
         HIPC(hipGetLastError());
-        HIPC(hipEventRecord(w.evk1, s));
+        HIPC(hipEventRecord(evk1, s));
         hipLaunchKernelGGL(k_gather_landmarks, dim3((unsigned)k, (unsigned)lc), dim3(256), 0, s, dm, n, (int)k, d_idx + l0 * k,
                            R->sub_dev + l0 * k * k, d_dp);
         HIPC(hipGetLastError());
@@ -172,18 +132,18 @@ extern "C" int tda_greedy_perm(const tda_greedy_args* a, tda_greedy_result** out
         if (l0 + lc < L) {  // the next chunk reuses the buffers and the two kernel events
             HIPC(hipStreamSynchronize(s));
             float ms = 0.0f;
-            HIPC(hipEventElapsedTime(&ms, w.evk0, w.evk1));
+            HIPC(hipEventElapsedTime(&ms, evk0, evk1));
             select_ms += ms;
         }
     }
     HIPC(hipMemcpyAsync(R->idx.get(), d_idx, L * k * 8, hipMemcpyDeviceToHost, s));
     HIPC(hipMemcpyAsync(R->lam.get(), d_lam, L * k * 4, hipMemcpyDeviceToHost, s));
-    HIPC(hipEventRecord(w.ev1, s));
+    HIPC(hipEventRecord(ev1, s));
     HIPC(hipStreamSynchronize(s));
     float ms = 0.0f;
-    HIPC(hipEventElapsedTime(&ms, w.evk0, w.evk1));
+    HIPC(hipEventElapsedTime(&ms, evk0, evk1));
     select_ms += ms;
-    HIPC(hipEventElapsedTime(&ms, w.ev0, w.ev1));
+    HIPC(hipEventElapsedTime(&ms, ev0, ev1));
     tda_greedy_result& r = R->pub;
     r.L = a->L;
     r.N = a->N;

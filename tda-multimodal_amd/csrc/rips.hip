@@ -1667,6 +1667,7 @@ int tda_device_ok(int32_t device) {
 
 }  // extern "C"
 
+#include "aux_ws.h"  // the per-device workspace of the five entries below, and its locking
 // UMAP embedding (include/tda_umap.h): same library, same error state
 #include "umap_host.h"
 // effective dimensionality (include/tda_rips.h tda_effective_dim)

@@ -6,27 +6,6 @@
 
 namespace {
 
-struct UmapWs {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t evin = nullptr;
-    char* buf = nullptr;
-    size_t cap = 0;
-    std::mutex mu;
-};
-std::mutex g_umap_mu;
-std::vector<UmapWs*> g_umap_ws;
-
-UmapWs& umap_ws(int dev) {
-    std::lock_guard<std::mutex> g(g_umap_mu);
-    for (auto* w : g_umap_ws)
-        if (w->device == dev) return *w;
-    auto* w = new UmapWs();
-    w->device = dev;
-    g_umap_ws.push_back(w);
-    return *w;
-}
-
 int umap_validate(const tda_umap_args* a) {
     if (!a) return fail(TDA_E_INVALID, "args is NULL");
     if (!a->x || !a->out) return fail(TDA_E_INVALID, "x and out are required");
@@ -73,36 +52,23 @@ void umap_distances(const void* x, int dtype, int metric, int64_t L, int64_t N, 
 extern "C" int tda_umap_batch(const tda_umap_args* a) {
     if (int rc = umap_validate(a)) return rc;
     if (!tda_device_ok(a->device)) return fail(TDA_E_NODEVICE, "no gfx950 device at ordinal " + std::to_string(a->device));
-    HIPC(hipSetDevice(a->device));
-    UmapWs& w = umap_ws(a->device);
+    AuxWs& w = aux_ws(kAuxUmap, a->device);
     std::lock_guard<std::mutex> guard(w.mu);
-    if (!w.stream) HIPC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    if (int rc = aux_open(w)) return rc;
     const int64_t L = a->L, N = a->N, D = a->D, k = a->n_neighbors, c = a->n_components;
     const size_t esz = a->dtype == TDA_F64 ? 8 : 4;
     const uint64_t ecap = (uint64_t)align_up((uint64_t)(2 * N * k), 64);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o = align_up(o + bytes, 256);
-        return r;
-    };
-    const size_t o_x = take(a->x_on_device ? 0 : L * N * D * esz), o_dist = take(L * N * N * 4), o_rmax = take(L * N * 4),
-                 o_kd = take(L * N * k * 4), o_ki = take(L * N * k * 4), o_P = take(L * N * N * 4), o_S = take(L * N * N * 4),
-                 o_smax = take(L * 4), o_ne = take(L * 4), o_head = take(L * ecap * 4), o_tail = take(L * ecap * 4),
-                 o_eps = take(L * ecap * 8), o_nxt = take(L * ecap * 8), o_nxn = take(L * ecap * 8), o_deg = take(L * N * 4),
-                 o_emb = take(L * N * c * 4);
-    if (w.cap < o) {
-        if (w.buf) HIPC(hipFree(w.buf));
-        w.buf = nullptr;
-        HIPC(hipMalloc(&w.buf, o));
-        w.cap = o;
-    }
+    Carve cv;
+    const size_t o_x = cv.take(a->x_on_device ? 0 : L * N * D * esz), o_dist = cv.take(L * N * N * 4), o_rmax = cv.take(L * N * 4),
+                 o_kd = cv.take(L * N * k * 4), o_ki = cv.take(L * N * k * 4), o_P = cv.take(L * N * N * 4), o_S = cv.take(L * N * N * 4),
+                 o_smax = cv.take(L * 4), o_ne = cv.take(L * 4), o_head = cv.take(L * ecap * 4), o_tail = cv.take(L * ecap * 4),
+                 o_eps = cv.take(L * ecap * 8), o_nxt = cv.take(L * ecap * 8), o_nxn = cv.take(L * ecap * 8), o_deg = cv.take(L * N * 4),
+                 o_emb = cv.take(L * N * c * 4);
+    if (int rc = aux_reserve(w, cv.o)) return rc;
     char* B = w.buf;
     hipStream_t s = w.stream;
-    if (a->x_on_device) {  // device inputs: read after the caller's queued work (NULL = the null stream)
-        if (!w.evin) HIPC(hipEventCreateWithFlags(&w.evin, hipEventDisableTiming));
-        if (int rc = order_after_caller(s, w.evin, a->stream, a->device)) return rc;
-    }
+    if (a->x_on_device)
+        if (int rc = aux_after_caller(w, a->stream)) return rc;
     const void* x = a->x;
     if (!a->x_on_device) {
         HIPC(hipMemcpyAsync(B + o_x, a->x, (size_t)L * N * D * esz, hipMemcpyHostToDevice, s));
@@ -153,8 +119,8 @@ extern "C" int tda_umap_batch(const tda_umap_args* a) {
     const int B2 = (int)c + 3;
     const size_t spec_lds = ((size_t)2 * B2 + 1) * N * 4;
     const bool spectral = a->init == TDA_UMAP_INIT_SPECTRAL && N <= kUmapSpecMaxN && spec_lds <= 150 * 1024;
-    HIPC(hipFuncSetAttribute((const void*)k_umap_spectral, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    HIPC(hipFuncSetAttribute((const void*)k_umap_sgd, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    if (int rc = aux_lds_attr(w, (const void*)k_umap_spectral, 150 * 1024)) return rc;
+    if (int rc = aux_lds_attr(w, (const void*)k_umap_sgd, 150 * 1024)) return rc;
     const int spec_iters = test_env("TDA_UMAP_SPEC_ITERS") ? atoi(test_env("TDA_UMAP_SPEC_ITERS")) : 300;
     hipLaunchKernelGGL(k_umap_spectral, dim3((unsigned)L), dim3(kUmapT), spectral ? spec_lds : 0, s, u, spec_iters, a->seed,
                        spectral ? 0 : 1);
@@ -190,33 +156,21 @@ extern "C" int tda_umap_transform(const tda_umap_transform_args* a) {
     if (a->n_epochs < 1 || a->negative_sample_rate < 0) return fail(TDA_E_INVALID, "n_epochs >= 1, negative_sample_rate >= 0");
     if (!(a->a > 0.0f) || !(a->b > 0.0f)) return fail(TDA_E_INVALID, "a, b must be positive");
     if (!tda_device_ok(a->device)) return fail(TDA_E_NODEVICE, "no gfx950 device at ordinal " + std::to_string(a->device));
-    HIPC(hipSetDevice(a->device));
-    UmapWs& w = umap_ws(a->device);
+    AuxWs& w = aux_ws(kAuxUmap, a->device);
     std::lock_guard<std::mutex> guard(w.mu);
-    if (!w.stream) HIPC(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    if (int rc = aux_open(w)) return rc;
     hipStream_t s = w.stream;
-    if (a->x_on_device) {  // device inputs: read after the caller's queued work (NULL = the null stream)
-        if (!w.evin) HIPC(hipEventCreateWithFlags(&w.evin, hipEventDisableTiming));
-        if (int rc = order_after_caller(s, w.evin, a->stream, a->device)) return rc;
-    }
+    if (a->x_on_device)
+        if (int rc = aux_after_caller(w, a->stream)) return rc;
     const size_t esz = a->dtype == TDA_F64 ? 8 : 4;
     const uint64_t ecap = (uint64_t)M * k;
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t r = o;
-        o = align_up(o + bytes, 256);
-        return r;
-    };
-    const size_t o_xt = take(a->x_on_device ? 0 : N * D * esz), o_y = take(a->x_on_device ? 0 : L * M * D * esz),
-                 o_z = take(L * NM * D * esz), o_dist = take(L * NM * NM * 4), o_rmax = take(L * NM * 4), o_kd = take(L * M * k * 4),
-                 o_ki = take(L * M * k * 4), o_val = take(L * M * k * 4), o_eps = take(L * ecap * 8), o_nxt = take(L * ecap * 8),
-                 o_nxn = take(L * ecap * 8), o_temb = take(N * c * 4), o_emb = take(L * M * c * 4);
-    if (w.cap < o) {
-        if (w.buf) HIPC(hipFree(w.buf));
-        w.buf = nullptr;
-        HIPC(hipMalloc(&w.buf, o));
-        w.cap = o;
-    }
+    Carve cv;
+    const size_t o_xt = cv.take(a->x_on_device ? 0 : N * D * esz), o_y = cv.take(a->x_on_device ? 0 : L * M * D * esz),
+                 o_z = cv.take(L * NM * D * esz), o_dist = cv.take(L * NM * NM * 4), o_rmax = cv.take(L * NM * 4),
+                 o_kd = cv.take(L * M * k * 4), o_ki = cv.take(L * M * k * 4), o_val = cv.take(L * M * k * 4),
+                 o_eps = cv.take(L * ecap * 8), o_nxt = cv.take(L * ecap * 8), o_nxn = cv.take(L * ecap * 8),
+                 o_temb = cv.take(N * c * 4), o_emb = cv.take(L * M * c * 4);
+    if (int rc = aux_reserve(w, cv.o)) return rc;
     char* B = w.buf;
     const void* xt = a->x_train;
     const void* y = a->y;
@@ -253,7 +207,7 @@ extern "C" int tda_umap_transform(const tda_umap_transform_args* a) {
     u.ncand = (int)N;
     hipLaunchKernelGGL(k_umap_knn, dim3((unsigned)((M + kUmapKnnT - 1) / kUmapKnnT), (unsigned)L), dim3(kUmapKnnT), 0, s, u);
     HIPC(hipGetLastError());
-    HIPC(hipFuncSetAttribute((const void*)k_umap_transform, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+    if (int rc = aux_lds_attr(w, (const void*)k_umap_transform, 150 * 1024)) return rc;
     hipLaunchKernelGGL(k_umap_transform, dim3((unsigned)L), dim3(kUmapT), lds, s, u, (const float*)(B + o_temb), (int)N,
                        (float*)(B + o_val), (double)a->a, (double)a->b, (double)a->learning_rate, (double)a->repulsion_strength,
                        a->negative_sample_rate, a->seed, a->disconnection);

@@ -1,0 +1,180 @@
+"""The host plan of the two diagram distances (csrc/dgm_plan.h: dgm_check_layout, dgm_gather,
+dgm_classify) against a numpy restatement (CPU).
+
+tests/dgm_plan_main.cpp includes only dgm_plan.h; it is compiled with g++ under the address and
+undefined-behaviour sanitizers and run once per test as a program of its own.  The class limits are
+those of dgm_host.h (a pair's n1 + n2: 128 / 1024 / 4096) and bn_host.h (max(n1, n2): 64 / 256 / 512).
+"""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "tda-multimodal_amd", "csrc")
+
+SUM, MAX = 0, 1
+LIMITS = {SUM: (128, 1024, 4096), MAX: (64, 256, 512)}
+INVALID, UNSUPPORTED = -1, -2
+
+
+@pytest.fixture(scope="module")
+def plan_exe(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("dgm_plan") / "dgm_plan")
+    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", "-I" + CSRC, "-o", exe, os.path.join(ROOT, "tests", "dgm_plan_main.cpp")], check=True)
+    return exe
+
+
+def run(exe, cases):
+    """cases: (measure, offsets, points (rows, 2) or None, pairs (P, 2), None (every i < j) or "negative P")
+    -> per case ("err", code, message) or ("ok", {name: values})"""
+    text = []
+    for measure, off, pts, pairs in cases:
+        t = [measure, *LIMITS[measure], len(off) - 1, *off]
+        t += [-1] if pts is None else [len(pts), *(repr(float(x)) for x in np.asarray(pts, np.float64).ravel())]
+        t += [-1] if pairs is None else [-2] if isinstance(pairs, str) else [len(pairs), *np.asarray(pairs).ravel()]
+        text.append(" ".join(map(str, t)))
+    r = subprocess.run([exe], input="\n".join(text) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]  # a sanitizer report ends the program with a non-zero status
+    lines, out = r.stdout.split("\n"), []
+    while lines and lines[0]:
+        head = lines.pop(0).split(" ", 2)
+        if head[0] == "err":
+            out.append(("err", int(head[1]), head[2]))
+            continue
+        assert head == ["ok"]
+        got = {}
+        for name in ("pts", "off", "pairs", "order", "cls_cnt", "cls_n"):
+            f = lines.pop(0).split()
+            assert f[0] == name
+            got[name] = [float(x) for x in f[1:]] if name == "pts" else [int(x) for x in f[1:]]
+        out.append(("ok", got))
+    assert len(out) == len(cases)
+    return out
+
+
+def expected(measure, off, pts, pairs):
+    """The plan restated: finite rows kept, every i < j for pairs None, a pair's class the first
+    limit its size fits, the order stable within a class."""
+    S = len(off) - 1
+    pts = np.zeros((0, 2)) if pts is None else np.asarray(pts, np.float64).reshape(-1, 2)
+    finite = np.isfinite(pts).all(1)
+    cnt = np.array([finite[off[s]:off[s + 1]].sum() for s in range(S)], np.int64)
+    if pairs is None:
+        pairs = [(i, j) for i in range(S) for j in range(i + 1, S)]
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    if ((pairs < 0) | (pairs >= S)).any():
+        return "err", INVALID, "pairs holds an index outside [0, S)"
+    n1, n2 = cnt[pairs[:, 0]], cnt[pairs[:, 1]]
+    n = n1 + n2 if measure == SUM else np.maximum(n1, n2)
+    lim = np.array(LIMITS[measure])
+    if (n > lim[-1]).any():
+        return "err", UNSUPPORTED, "too large"
+    cls = np.searchsorted(lim, n, side="left")  # the first class with n <= its limit
+    return "ok", {
+        "pts": pts[:off[S]][finite[:off[S]]].ravel().tolist(),
+        "off": np.concatenate([[0], np.cumsum(cnt)]).tolist(),
+        "pairs": pairs.ravel().tolist(),
+        "order": np.argsort(cls, kind="stable").tolist(),
+        "cls_cnt": np.bincount(cls, minlength=3).tolist(),
+        "cls_n": [int(n[cls == c].max()) if (cls == c).any() else 0 for c in range(3)],
+    }
+
+
+def diagrams(sizes, seed=0, junk=()):
+    """offsets and points of diagrams of the given numbers of finite rows; diagram s in `junk`
+    also gets three non-finite rows (at its start, in its middle and at its end)."""
+    rng = np.random.default_rng(seed)
+    rows, off = [], [0]
+    for s, n in enumerate(sizes):
+        b = rng.uniform(0, 5, n)
+        d = np.stack([b, b + rng.uniform(0.1, 5, n)], 1)
+        if s in junk:
+            d = np.concatenate([[[np.nan, 1.0]], d[:n // 2], [[0.5, np.inf]], d[n // 2:], [[-np.inf, np.inf]]])
+        rows.append(d)
+        off.append(off[-1] + len(d))
+    return off, np.concatenate(rows) if rows else np.zeros((0, 2))
+
+
+def check(exe, cases):
+    for case, got in zip(cases, run(exe, cases)):
+        exp = expected(*case)
+        assert got == exp, (case[0], case[1], case[3])
+    return [expected(*c) for c in cases]
+
+
+@pytest.mark.parametrize("measure", (SUM, MAX))
+def test_all_pairs_expansion(plan_exe, measure):
+    cases = []
+    for S in (0, 1, 2, 5):
+        off, pts = diagrams([3, 0, 70, 5, 300][:S], seed=S)
+        cases.append((measure, off, pts, None))
+    exp = check(plan_exe, cases)
+    assert [len(e[1]["pairs"]) // 2 for e in exp] == [0, 0, 1, 10]
+    assert exp[3][1]["pairs"][:6] == [0, 1, 0, 2, 0, 3]  # row-major, i < j
+
+
+@pytest.mark.parametrize("measure", (SUM, MAX))
+def test_explicit_pairs_with_repeats_and_self_pairs(plan_exe, measure):
+    off, pts = diagrams([3, 200, 70, 5, 600 if measure == SUM else 300, 0], seed=7, junk=(1, 3))
+    pairs = [(4, 4), (0, 1), (1, 0), (0, 1), (3, 3), (5, 5), (2, 4), (5, 0), (4, 1), (0, 3), (4, 4)]
+    exp = check(plan_exe, [(measure, off, pts, pairs), (measure, off, pts, [])])
+    assert sorted(exp[0][1]["order"]) == list(range(len(pairs))) and min(exp[0][1]["cls_cnt"]) > 0  # all three classes
+    assert exp[1][1]["order"] == [] and exp[1][1]["cls_n"] == [0, 0, 0]
+
+
+@pytest.mark.parametrize("measure", (SUM, MAX))
+def test_non_finite_rows_are_dropped(plan_exe, measure):
+    nan, inf = np.nan, np.inf
+    pts = [[0, 1], [nan, 1], [0, nan], [1, 2], [inf, 3], [1, inf], [-inf, 0], [0, -inf], [2, 3], [nan, inf],  # diagram 0: 3 finite
+           [0, inf], [nan, nan], [-inf, inf],  # diagram 1: empty after the filter
+           [4, 5]]
+    off = [0, 10, 13, 13, 14]  # diagram 2 has no rows at all
+    exp = check(plan_exe, [(measure, off, pts, None), (measure, off, pts, [(1, 2), (1, 1), (2, 0)])])
+    assert exp[0][1]["off"] == [0, 3, 3, 3, 4] and exp[0][1]["pts"] == [0, 1, 1, 2, 2, 3, 4, 5]
+    assert exp[1][1]["cls_n"] == [3, 0, 0]
+    # the same rows with junk spread over larger diagrams
+    off, pts = diagrams([40, 25, 0, 130], seed=3, junk=(0, 2, 3))
+    check(plan_exe, [(measure, off, pts, None)])
+
+
+def test_class_limits_of_the_sum(plan_exe):
+    """n1 + n2 = 128 / 129, 1024 / 1025, 4096 / 4097; the non-finite rows do not count."""
+    off, pts = diagrams([64, 64, 65, 512, 512, 513, 2048, 2048, 2049], seed=1, junk=(1, 5, 7))
+    pairs = [(6, 7), (0, 1), (3, 5), (0, 2), (3, 4), (1, 0)]
+    exp = check(plan_exe, [(SUM, off, pts, pairs), (SUM, off, pts, pairs + [(6, 8)]), (SUM, off, pts, [(8, 7)])])
+    assert exp[0][1]["cls_n"] == [128, 1024, 4096] and exp[0][1]["cls_cnt"] == [2, 2, 2] and exp[0][1]["order"] == [1, 5, 3, 4, 0, 2]
+    assert exp[1] == exp[2] == ("err", UNSUPPORTED, "too large")
+
+
+def test_class_limits_of_the_max(plan_exe):
+    """max(n1, n2) = 64 / 65, 256 / 257, 512 / 513, the longer diagram on either side."""
+    off, pts = diagrams([64, 65, 256, 257, 512, 513, 0], seed=2, junk=(0, 2, 4))
+    pairs = [(4, 3), (0, 0), (1, 0), (2, 0), (3, 2), (6, 4), (0, 6), (0, 1)]
+    exp = check(plan_exe, [(MAX, off, pts, pairs), (MAX, off, pts, pairs + [(5, 6)]), (MAX, off, pts, [(0, 5)])])
+    assert exp[0][1]["cls_n"] == [64, 256, 512] and exp[0][1]["cls_cnt"] == [2, 3, 3] and exp[0][1]["order"] == [1, 6, 2, 3, 7, 0, 4, 5]
+    assert exp[1] == exp[2] == ("err", UNSUPPORTED, "too large")
+
+
+def test_layout_errors_and_their_messages(plan_exe):
+    off, pts = diagrams([3, 4, 5], seed=5)
+    cases = [
+        (SUM, [1, 3, 7, 12], pts, None),
+        (SUM, [0, 7, 3, 12], pts, None),
+        (MAX, [0, 3, 7, 6], pts, [(0, 1)]),
+        (SUM, off, None, None),
+        (MAX, off, pts, "negative P"),
+        (SUM, off, pts, [(0, 3)]),
+        (MAX, off, pts, [(0, 1), (-1, 0)]),
+        (SUM, [1, 0, 7, 12], None, "negative P"),  # the checks in their order: offsets[0] first
+        (SUM, [0, 7, 3, 12], None, "negative P"),
+        (SUM, off, None, "negative P"),
+    ]
+    msgs = ["offsets[0] must be 0", "offsets must be non-decreasing", "offsets must be non-decreasing", "points is NULL",
+            "P must be >= 0", "pairs holds an index outside [0, S)", "pairs holds an index outside [0, S)",
+            "offsets[0] must be 0", "offsets must be non-decreasing", "points is NULL"]
+    assert run(plan_exe, cases) == [("err", INVALID, m) for m in msgs]
+    # no rows at all: points may be NULL
+    assert run(plan_exe, [(SUM, [0, 0, 0], None, None)])[0] == expected(SUM, [0, 0, 0], None, None)
