@@ -9,10 +9,10 @@ import sys as _sys
 
 from . import diagrams, distributed, metrics, synthetic, umap  # noqa: F401
 from .diagrams import (bottleneck, bottleneck_matrix, sliced_wasserstein, sliced_wasserstein_kernel,  # noqa: F401
-                       sliced_wasserstein_matrix)
+                       sliced_wasserstein_matrix, wasserstein, wasserstein_matrix)
 from .metrics import (compute_effective_dimensionality, compute_fixed_window_ed, compute_fixed_window_id,  # noqa: F401
                       compute_intrinsic_dimensionality, matrix_entropy, matrix_entropy_profile)
-from ._lib import BOTTLENECK_EXPORTS, DGM_EXPORTS, EXPORTS, LIB_PATH, build, lib  # noqa: F401
+from ._lib import BOTTLENECK_EXPORTS, DGM_EXPORTS, EXPORTS, LIB_PATH, WASSERSTEIN_EXPORTS, build, lib  # noqa: F401
 from .pipeline import (get_max_persistence, get_persistence, layer_distance_matrix, layer_record,  # noqa: F401
                        layer_record_adversarial, peak_layer, run_adversarial_condition, run_sweep, write_layer_stats,
                        write_summary_stats)
@@ -46,6 +46,8 @@ __all__ = [
     "sliced_wasserstein_kernel",
     "bottleneck",
     "bottleneck_matrix",
+    "wasserstein",
+    "wasserstein_matrix",
     "silhouette_score",
     "compute_intrinsic_dimensionality",
     "compute_effective_dimensionality",

@@ -235,6 +235,32 @@ class BnResult(ctypes.Structure):  # include/tda_dgm.h tda_bn_result
 TDA_BN_MAX_POINTS = 512  # finite points of one diagram
 
 
+class WsArgs(ctypes.Structure):  # include/tda_dgm.h tda_ws_args
+    _fields_ = [
+        ("points", ctypes.c_void_p),
+        ("offsets", ctypes.c_void_p),
+        ("S", ctypes.c_int64),
+        ("pairs", ctypes.c_void_p),
+        ("P", ctypes.c_int64),
+        ("device", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+    ]
+
+
+class WsResult(ctypes.Structure):  # include/tda_dgm.h tda_ws_result
+    _fields_ = [
+        ("P", ctypes.c_int64),
+        ("dist", ctypes.POINTER(ctypes.c_double)),
+        ("device_ms", ctypes.c_double),
+        ("match_off", _i64p),
+        ("match", ctypes.POINTER(ctypes.c_int32)),
+    ]
+
+
+TDA_WS_MAX_POINTS = 512  # finite points of one diagram
+TDA_WS_WANT_MATCHING = 1
+
+
 class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
     _fields_ = [
         ("x_train", ctypes.c_void_p),
@@ -271,6 +297,8 @@ EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "
 DGM_EXPORTS = ("tda_sliced_wasserstein", "tda_sw_free")
 # the bottleneck symbols of include/tda_dgm.h
 BOTTLENECK_EXPORTS = ("tda_bottleneck", "tda_bn_free")
+# the Wasserstein symbols of include/tda_dgm.h
+WASSERSTEIN_EXPORTS = ("tda_wasserstein", "tda_ws_free")
 
 _lib = None
 
@@ -403,6 +431,10 @@ def lib():
     L.tda_bottleneck.restype = ctypes.c_int
     L.tda_bn_free.argtypes = [ctypes.POINTER(BnResult)]
     L.tda_bn_free.restype = None
+    L.tda_wasserstein.argtypes = [ctypes.POINTER(WsArgs), ctypes.POINTER(ctypes.POINTER(WsResult))]
+    L.tda_wasserstein.restype = ctypes.c_int
+    L.tda_ws_free.argtypes = [ctypes.POINTER(WsResult)]
+    L.tda_ws_free.restype = None
     _lib = L
     return L
 

@@ -1,11 +1,13 @@
-// dgm_plan.h -- the host plan of a call of include/tda_dgm.h (tda_sliced_wasserstein, tda_bottleneck):
-// the layout checks, the finite points and the pair list, and the pairs sorted into size classes.
+// dgm_plan.h -- the host plan of a call of include/tda_dgm.h (tda_sliced_wasserstein, tda_bottleneck,
+// tda_wasserstein): the layout checks, the finite points and the pair list, the pairs sorted into size
+// classes, and (tda_wasserstein) each pair's canonical orientation.
 // Plain C++, no HIP: a function returns an error code and leaves its message in `msg`
 // (tests/dgm_plan_main.cpp runs every case with a host compiler alone).
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -99,6 +101,36 @@ inline int dgm_classify(PairPlan& pl, PairSize measure, const int (&limits)[kPai
     }
     for (int64_t p = 0; p < pl.P; ++p) pl.order[at[cls[p]]++] = (int32_t)p;
     return 0;
+}
+
+// Orients every gathered pair canonically, for a kernel that has to see the same input for (i, j) and
+// (j, i): the diagram with more finite points first and, at equal counts, the one whose finite points
+// (b0, d0, b1, d1, ...) come first lexicographically (by value, -0 below +0, so that equal means the
+// same bits).  swapped[p] = 1 where the two entries of pair p in pl.pairs were exchanged.
+inline void dgm_orient(PairPlan& pl, std::vector<uint8_t>& swapped) {
+    auto key = [](double x) {  // finite doubles as integers in the order of their values
+        uint64_t b;
+        std::memcpy(&b, &x, 8);
+        return b >> 63 ? ~b : b | (uint64_t)1 << 63;
+    };
+    swapped.assign((size_t)pl.P, 0);
+    for (int64_t p = 0; p < pl.P; ++p) {
+        const int32_t i = pl.pairs[2 * p], j = pl.pairs[2 * p + 1];
+        const int64_t n1 = pl.off[i + 1] - pl.off[i], n2 = pl.off[j + 1] - pl.off[j];
+        bool swap = n2 > n1;
+        if (n1 == n2 && i != j) {
+            const double *a = pl.pts.data() + 2 * pl.off[i], *b = pl.pts.data() + 2 * pl.off[j];
+            for (int64_t k = 0; k < 2 * n1; ++k)
+                if (key(a[k]) != key(b[k])) {
+                    swap = key(b[k]) < key(a[k]);
+                    break;
+                }
+        }
+        if (swap) {
+            std::swap(pl.pairs[2 * p], pl.pairs[2 * p + 1]);
+            swapped[p] = 1;
+        }
+    }
 }
 
 }  // namespace tda

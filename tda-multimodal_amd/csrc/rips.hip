@@ -1667,7 +1667,7 @@ int tda_device_ok(int32_t device) {
 
 }  // extern "C"
 
-#include "aux_ws.h"  // the per-device workspace of the five entries below, and its locking
+#include "aux_ws.h"  // the per-device workspace of the six entries below, and its locking
 // UMAP embedding (include/tda_umap.h): same library, same error state
 #include "umap_host.h"
 // effective dimensionality (include/tda_rips.h tda_effective_dim)
@@ -1678,3 +1678,5 @@ int tda_device_ok(int32_t device) {
 #include "dgm_host.h"
 // bottleneck distances between persistence diagrams (include/tda_dgm.h)
 #include "bn_host.h"
+// 1-Wasserstein distances between persistence diagrams (include/tda_dgm.h)
+#include "ws_host.h"

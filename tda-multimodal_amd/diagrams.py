@@ -25,6 +25,17 @@ a matched pair paying max(|b_p - b_q|, |d_p - d_q|) and an unmatched point its
 distance to the diagonal |d - b| / 2, so that d_B(A, empty) is half of A's
 maximum persistence.  The value is exact (one of those costs, bit for bit) and
 a diagram may hold 512 finite points.
+
+``wasserstein`` is ``persim.wasserstein(dgm1, dgm2, matching=False)`` [upstream]
+and ``wasserstein_matrix`` its sweep-level form: the optimal-transport distance
+in which every bar counts,
+
+    W(A, B) = min over partial matchings of the sum of the costs paid,
+
+a matched pair paying its Euclidean distance and an unmatched point its L2
+distance to the diagonal (d - b) / sqrt(2).  The solver is exact up to the
+rounding of its float64 duals (tda_dgm.h states the bounds); the matching can
+be returned, and a diagram may hold 512 finite points.
 """
 from __future__ import annotations
 
@@ -227,6 +238,107 @@ def bottleneck(dgm1, dgm2, matching: bool = False, device: int = 0) -> float:
         if isinstance(d, LayerResult):
             raise ValueError("dgm1 and dgm2 are (n, 2) arrays (for LayerResults: bottleneck_matrix)")
     return float(bottleneck_matrix([dgm1], other=[dgm2], device=device)[0, 0])
+
+
+_SQRT1_2 = 0.70710678118654752440  # the factor of a point's L2 distance to the diagonal (tda_dgm.h)
+
+
+def _call_ws(points, offsets, pairs, device: int, want_matching: bool = False):
+    """One tda_wasserstein call: (dist (P,), device_ms, match_off (P + 1,) or None, match or None)."""
+    S = len(offsets) - 1
+    if (S < 2) if pairs is None else not len(pairs):  # no pair: nothing to launch
+        return np.zeros(0), 0.0, None, None
+    a = _lib.WsArgs()
+    a.points = points.ctypes.data if len(points) else None
+    a.offsets = offsets.ctypes.data
+    a.S = S
+    if pairs is not None:
+        a.pairs, a.P = pairs.ctypes.data, len(pairs)
+    a.device, a.flags = int(device), _lib.TDA_WS_WANT_MATCHING if want_matching else 0
+    L = _lib.lib()
+    res = ctypes.POINTER(_lib.WsResult)()
+    _lib.check(L.tda_wasserstein(ctypes.byref(a), ctypes.byref(res)))
+    try:
+        r = res.contents
+        out = np.frombuffer(ctypes.string_at(r.dist, r.P * 8), dtype=np.float64).copy() if r.P else np.zeros(0)
+        moff = match = None
+        if want_matching:
+            moff = np.frombuffer(ctypes.string_at(r.match_off, (r.P + 1) * 8), dtype=np.int64).copy()
+            match = np.frombuffer(ctypes.string_at(r.match, int(moff[-1]) * 4), dtype=np.int32).copy()
+        return out, float(r.device_ms), moff, match
+    finally:
+        L.tda_ws_free(res)
+
+
+def _ws_inputs(dgms, other, dim: int):
+    """(points, offsets, pairs or None, S, S') of a Wasserstein call, the limit checked and the
+    non-finite points reported."""
+    pts, off = _flatten(dgms, dim)
+    S = S2 = len(off) - 1
+    if other is None:
+        pairs = None
+        cnt, dropped = _finite_counts(pts, off)
+        top = cnt.max() if S >= 2 else 0
+    else:
+        pts2, off2 = _flatten(other, dim)
+        S2 = len(off2) - 1
+        pts, off = np.concatenate([pts, pts2]), np.concatenate([off, off[-1] + off2[1:]])
+        pairs = np.stack(np.meshgrid(np.arange(S), S + np.arange(S2), indexing="ij"), -1).reshape(-1, 2).astype(np.int32)
+        cnt, dropped = _finite_counts(pts, off)
+        top = cnt.max() if S and S2 else 0
+    if top > _lib.TDA_WS_MAX_POINTS:
+        raise NotImplementedError(f"a diagram holds {int(top)} finite points: more than {_lib.TDA_WS_MAX_POINTS} is not supported")
+    if dropped:
+        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
+    return pts, off, pairs, S, S2
+
+
+def wasserstein_matrix(dgms, other=None, device: int = 0, dim: int = 1, return_time: bool = False):
+    """Wasserstein distances between every pair of diagrams, one library call.
+
+    The arguments and the result are those of :func:`bottleneck_matrix`: ``dgms``
+    and ``other`` are lists of (n, 2) arrays or of :class:`LayerResult`; the
+    (S, S) matrix is symmetric with a zero diagonal, the (S, S') matrix is
+    ``dgms`` against ``other``.  A value is the same bits in any call that holds
+    the pair, in either orientation."""
+    pts, off, pairs, S, S2 = _ws_inputs(dgms, other, dim)
+    dist, ms, _, _ = _call_ws(pts, off, pairs, device)
+    if other is None:
+        D = np.zeros((S, S))
+        iu = np.triu_indices(S, 1)  # row-major i < j: the order of the library's all-pairs result
+        D[iu] = dist
+        D = D + D.T
+    else:
+        D = dist.reshape(S, S2)
+    return (D, ms) if return_time else D
+
+
+def wasserstein(dgm1, dgm2, matching: bool = False, device: int = 0):
+    """``persim.wasserstein(dgm1, dgm2, matching=False)`` [upstream] on the GPU:
+    the 1-Wasserstein distance (Euclidean ground metric) of two (n, 2) diagrams.
+    Points with a non-finite coordinate are ignored, with a warning.  With
+    ``matching`` the result is ``(distance, (K, 3) float64 array)`` of rows
+    ``[i, j, cost]`` as persim returns them: the points of ``dgm1`` in their
+    order, each with its partner in ``dgm2`` or -1 for the diagonal, then
+    ``[-1, j, cost]`` for the points of ``dgm2`` left to the diagonal.  The
+    indices count the rows with a finite (birth, death)."""
+    for d in (dgm1, dgm2):
+        if isinstance(d, LayerResult):
+            raise ValueError("dgm1 and dgm2 are (n, 2) arrays (for LayerResults: wasserstein_matrix)")
+    pts, off, pairs, _, _ = _ws_inputs([dgm1], [dgm2], 1)
+    dist, _, _, match = _call_ws(pts, off, pairs, device, want_matching=bool(matching))
+    if not matching:
+        return float(dist[0])
+    A, B = (d[np.isfinite(d).all(axis=1)] for d in (pts[:off[1]], pts[off[1]:]))
+    i = np.arange(len(A))
+    hit = match >= 0
+    free = np.setdiff1d(np.arange(len(B)), match[hit])
+    db, dd = A[hit, 0] - B[match[hit], 0], A[hit, 1] - B[match[hit], 1]
+    cost = (A[:, 1] - A[:, 0]) * _SQRT1_2
+    cost[hit] = np.sqrt(db * db + dd * dd)
+    rows = np.concatenate([np.stack([i, match, cost], 1),
+                           np.stack([np.full(len(free), -1.0), free, (B[free, 1] - B[free, 0]) * _SQRT1_2], 1)])
+    return float(dist[0]), rows
 
 
 def sliced_wasserstein_kernel(D, sigma: float):
