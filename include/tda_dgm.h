@@ -1,5 +1,6 @@
 /*
- * tda_dgm.h -- distances between persistence diagrams on the MI355X (gfx950).
+ * tda_dgm.h -- distances between persistence diagrams, and their vectorisations
+ * (landscapes, images), on the MI355X (gfx950).
  * Part of libtda_rips.so: error codes, tda_last_error() and tda_device_ok()
  * are those of tda_rips.h.  Added to ABI 8 (new symbols only; no existing
  * struct changed).
@@ -94,6 +95,73 @@
  * TDA_E_INVALID.  All argument errors arrive before any device work.
  * TDA_E_CAPACITY: a pair's solver ran into one of the kernel's loop bounds (an
  * internal error; no result).
+ *
+ * tda_landscape: the persistence landscape (Bubenik 2015; persim.landscapes
+ * [upstream]) of S diagrams, sampled exactly on a grid, in one call.  For a
+ * diagram A, after dropping every row with a non-finite coordinate, and a grid
+ * value t:
+ *     f_p(t)   = max(0, min(t - b_p, d_p - t))             one tent per point
+ *     lambda_k(t) = the k-th largest of {f_p(t) : p in A}, k = 1 .. K; 0 when A has fewer than k points
+ *     values[s][k - 1][g] = lambda_k(grid[g])
+ * Everything is float64.  Each value is one correctly rounded subtraction of two
+ * inputs (t - b_p or d_p - t) or +0.0, never -0.0: the result is exact, equal bit
+ * for bit to a numpy restatement.  A row with d <= b contributes zeros only.
+ * This is the exact landscape at the grid values: nothing is snapped to the grid
+ * (persim's PersLandscapeApprox moves the bars to the grid first and so differs).
+ * grid holds G finite values in any order; the library forms no grid value itself.
+ *
+ * Limits: at most TDA_VEC_MAX_POINTS finite points per diagram, 1 <= K <=
+ * TDA_PL_MAX_DEPTH, 1 <= G <= TDA_PL_MAX_STEPS, S * K * G <= TDA_VEC_MAX_OUT and
+ * S <= TDA_SW_MAX_WORK, else TDA_E_UNSUPPORTED.  Bad offsets, grid == NULL, a
+ * non-finite grid value, K < 1, G < 1, reserved != 0: TDA_E_INVALID.  All argument
+ * errors arrive before any device work.
+ *
+ * tda_persistence_image: the persistence image (Adams et al. 2017;
+ * persim.PersistenceImager [upstream], with its default skew = True) of S diagrams
+ * in one call.  Finite rows only, in birth-persistence coordinates (b_p, pi_p),
+ * pi_p the float64 difference d_p - b_p:
+ *     w_p      = pi_p ^ weight_power for pi_p > 0, else 0       (1 for power 0, pi_p for power 1)
+ *     r        = 0.70710678118654752440 / sigma                  1 / (sigma sqrt(2))
+ *     gx_p[i]  = (erf((x_edges[i + 1] - b_p) r) - erf((x_edges[i] - b_p) r)) / 2
+ *     gy_p[j]  = the same with y_edges and pi_p
+ *     values[s][i][j] = sum over p of w_p gx_p[i] gy_p[j]         p in the order of the finite rows
+ * i is the birth axis (W pixels), j the persistence axis (H pixels): a Gaussian of
+ * standard deviation sigma in both axes (covariance sigma^2 I, which is what
+ * persim's kernel_params["sigma"] holds), integrated over each pixel.
+ *
+ * Accuracy: for every pixel |values - exact| <= C(n) u sum_p w_p, with n the
+ * diagram's finite points, u = 2^-53, the exact value that of the formulas above
+ * on the float64 b_p, pi_p and edges, and
+ *     C(n) = 2 E + 9 + n,    E = TDA_PI_ERF_ULP = 16.
+ * Derivation (first order in u; every step rounds up, which covers the u^2 terms):
+ *   1. the argument z = (edge - b) r is a rounded subtraction, r (a rounded
+ *      constant and a rounded division) and a rounded product: a relative error of
+ *      4 u, and |z erf'(z)| <= 0.49, so erf moves by at most 1.96 u <= 2 u;
+ *   2. the device erf is within E ulp, and an ulp of a value below 1 is at most u:
+ *      each erf value is within (2 + E) u of the exact one;
+ *   3. g = (e1 - e0) / 2 adds half of two such errors each way and one rounding of
+ *      a value <= 1: |g^ - g| <= (3 + E) u, with 0 <= g <= 1;
+ *   4. a term w gx gy: the weight is within one ulp, at most 2 u w (the host's pow;
+ *      exact for the powers 0 and 1), w gx is rounded once, the product with gy is
+ *      exact inside the fused multiply-add: with gx, gy <= 1 the term is within
+ *      (2 (3 + E) + 3) u w;
+ *   5. the n terms are non-negative up to those errors and are added one by one,
+ *      each addition rounding a partial sum that is at most the total: n u sum w.
+ * E: the ROCm install documents no bound for the device erf (no table of ulp
+ * errors ships with it), so E is the OpenCL conformance bound for double erf, 16
+ * ulp, which the device math library is built to meet.  C is not fitted to
+ * observed errors.
+ *
+ * Limits: TDA_VEC_MAX_POINTS as above, 1 <= W, H <= TDA_PI_MAX_PIXELS, S * W * H
+ * <= TDA_VEC_MAX_OUT, else TDA_E_UNSUPPORTED.  Edges that are NULL, non-finite or
+ * not strictly increasing, sigma not finite or <= 0, weight_power not finite or
+ * < 0, W or H < 1, reserved != 0: TDA_E_INVALID, before any device work.
+ *
+ * Promised by both, bit for bit: a diagram's output is the same alone, among other
+ * diagrams of any sizes (whatever size classes the call then holds), at any
+ * position in the call and from run to run; the image's sum over p runs in the
+ * order of the finite rows whatever the image shape's tiling.  An empty diagram
+ * gives +0.0 everywhere.
  */
 #ifndef TDA_DGM_H
 #define TDA_DGM_H
@@ -171,6 +239,57 @@ typedef struct tda_ws_result {
 
 int tda_wasserstein(const tda_ws_args *args, tda_ws_result **out);
 void tda_ws_free(tda_ws_result *r);
+
+#define TDA_VEC_MAX_POINTS 4096     /* finite points of one diagram          */
+#define TDA_VEC_MAX_OUT (1ll << 24) /* doubles of one call's result, S * F   */
+#define TDA_PL_MAX_DEPTH 64
+#define TDA_PL_MAX_STEPS 4096
+#define TDA_PI_MAX_PIXELS 256       /* per axis                              */
+#define TDA_PI_ERF_ULP 16           /* E of the accuracy bound C(n)          */
+
+typedef struct tda_pl_args {
+    const double *points;   /* host (total, 2) f64 (birth, death); non-finite rows are skipped */
+    const int64_t *offsets; /* host [S + 1] non-decreasing row boundaries, offsets[0] = 0      */
+    int64_t S;              /* diagrams                                                        */
+    const double *grid;     /* host [G] finite grid values, any order                          */
+    int32_t G;              /* 1 .. TDA_PL_MAX_STEPS                                           */
+    int32_t K;              /* depth, 1 .. TDA_PL_MAX_DEPTH                                    */
+    int32_t device;         /* HIP device ordinal                                              */
+    int32_t reserved;       /* must be 0                                                       */
+} tda_pl_args;
+
+typedef struct tda_pl_result {
+    int64_t S;            /* diagrams                                              */
+    int64_t F;            /* values per diagram, K * G                             */
+    const double *values; /* host [S][K][G]                                        */
+    double device_ms;     /* device time of the call (HIP events, copies included) */
+} tda_pl_result;
+
+int tda_landscape(const tda_pl_args *args, tda_pl_result **out);
+void tda_pl_free(tda_pl_result *r);
+
+typedef struct tda_pi_args {
+    const double *points;   /* host (total, 2) f64 (birth, death); non-finite rows are skipped */
+    const int64_t *offsets; /* host [S + 1] non-decreasing row boundaries, offsets[0] = 0      */
+    int64_t S;              /* diagrams                                                        */
+    const double *x_edges;  /* host [W + 1] finite, strictly increasing: the birth axis        */
+    const double *y_edges;  /* host [H + 1] finite, strictly increasing: the persistence axis  */
+    int32_t W, H;           /* pixels per axis, 1 .. TDA_PI_MAX_PIXELS                         */
+    double sigma;           /* finite, > 0                                                     */
+    double weight_power;    /* finite, >= 0                                                    */
+    int32_t device;         /* HIP device ordinal                                              */
+    int32_t reserved;       /* must be 0                                                       */
+} tda_pi_args;
+
+typedef struct tda_pi_result {
+    int64_t S;            /* diagrams                                              */
+    int64_t F;            /* values per diagram, W * H                             */
+    const double *values; /* host [S][W][H]                                        */
+    double device_ms;     /* device time of the call (HIP events, copies included) */
+} tda_pi_result;
+
+int tda_persistence_image(const tda_pi_args *args, tda_pi_result **out);
+void tda_pi_free(tda_pi_result *r);
 
 #ifdef __cplusplus
 }

@@ -261,6 +261,61 @@ TDA_WS_MAX_POINTS = 512  # finite points of one diagram
 TDA_WS_WANT_MATCHING = 1
 
 
+class PlArgs(ctypes.Structure):  # include/tda_dgm.h tda_pl_args
+    _fields_ = [
+        ("points", ctypes.c_void_p),
+        ("offsets", ctypes.c_void_p),
+        ("S", ctypes.c_int64),
+        ("grid", ctypes.c_void_p),
+        ("G", ctypes.c_int32),
+        ("K", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PlResult(ctypes.Structure):  # include/tda_dgm.h tda_pl_result
+    _fields_ = [
+        ("S", ctypes.c_int64),
+        ("F", ctypes.c_int64),
+        ("values", ctypes.POINTER(ctypes.c_double)),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
+class PiArgs(ctypes.Structure):  # include/tda_dgm.h tda_pi_args
+    _fields_ = [
+        ("points", ctypes.c_void_p),
+        ("offsets", ctypes.c_void_p),
+        ("S", ctypes.c_int64),
+        ("x_edges", ctypes.c_void_p),
+        ("y_edges", ctypes.c_void_p),
+        ("W", ctypes.c_int32),
+        ("H", ctypes.c_int32),
+        ("sigma", ctypes.c_double),
+        ("weight_power", ctypes.c_double),
+        ("device", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PiResult(ctypes.Structure):  # include/tda_dgm.h tda_pi_result
+    _fields_ = [
+        ("S", ctypes.c_int64),
+        ("F", ctypes.c_int64),
+        ("values", ctypes.POINTER(ctypes.c_double)),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
+TDA_VEC_MAX_POINTS = 4096  # finite points of one diagram
+TDA_VEC_MAX_OUT = 1 << 24  # doubles of one call's result
+TDA_PL_MAX_DEPTH = 64
+TDA_PL_MAX_STEPS = 4096
+TDA_PI_MAX_PIXELS = 256  # per axis
+TDA_PI_ERF_ULP = 16  # E of the image's accuracy bound C(n) = 2 E + 9 + n
+
+
 class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
     _fields_ = [
         ("x_train", ctypes.c_void_p),
@@ -299,6 +354,8 @@ DGM_EXPORTS = ("tda_sliced_wasserstein", "tda_sw_free")
 BOTTLENECK_EXPORTS = ("tda_bottleneck", "tda_bn_free")
 # the Wasserstein symbols of include/tda_dgm.h
 WASSERSTEIN_EXPORTS = ("tda_wasserstein", "tda_ws_free")
+# the landscape and image symbols of include/tda_dgm.h
+VECTOR_EXPORTS = ("tda_landscape", "tda_pl_free", "tda_persistence_image", "tda_pi_free")
 
 _lib = None
 
@@ -435,6 +492,14 @@ def lib():
     L.tda_wasserstein.restype = ctypes.c_int
     L.tda_ws_free.argtypes = [ctypes.POINTER(WsResult)]
     L.tda_ws_free.restype = None
+    L.tda_landscape.argtypes = [ctypes.POINTER(PlArgs), ctypes.POINTER(ctypes.POINTER(PlResult))]
+    L.tda_landscape.restype = ctypes.c_int
+    L.tda_pl_free.argtypes = [ctypes.POINTER(PlResult)]
+    L.tda_pl_free.restype = None
+    L.tda_persistence_image.argtypes = [ctypes.POINTER(PiArgs), ctypes.POINTER(ctypes.POINTER(PiResult))]
+    L.tda_persistence_image.restype = ctypes.c_int
+    L.tda_pi_free.argtypes = [ctypes.POINTER(PiResult)]
+    L.tda_pi_free.restype = None
     _lib = L
     return L
 

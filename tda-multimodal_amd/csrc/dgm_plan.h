@@ -1,6 +1,7 @@
 // dgm_plan.h -- the host plan of a call of include/tda_dgm.h (tda_sliced_wasserstein, tda_bottleneck,
 // tda_wasserstein): the layout checks, the finite points and the pair list, the pairs sorted into size
-// classes, and (tda_wasserstein) each pair's canonical orientation.
+// classes, and (tda_wasserstein) each pair's canonical orientation; and the per-diagram plan of
+// tda_landscape and tda_persistence_image (VecPlan, at the end).
 // Plain C++, no HIP: a function returns an error code and leaves its message in `msg`
 // (tests/dgm_plan_main.cpp runs every case with a host compiler alone).
 #pragma once
@@ -42,23 +43,27 @@ inline int dgm_check_layout(const double* points, const int64_t* offsets, int64_
     return 0;
 }
 
-// pl.pts / off: the finite points of the S diagrams (the essential classes dropped) with their row
-// boundaries; pl.pairs / P: the P pairs, copied and index-checked or, for pairs == NULL, every i < j in
-// row-major order.  offsets is valid (dgm_check_layout).
-inline int dgm_gather(const double* points, const int64_t* offsets, int64_t S, const int32_t* pairs, int64_t P, PairPlan& pl,
-                      std::string& msg) {
-    pl.P = P;
-    pl.off.assign((size_t)S + 1, 0);
-    pl.pts.reserve((size_t)offsets[S] * 2);
+// pts / off: the finite points of the S diagrams (the essential classes dropped) with their row boundaries
+inline void dgm_gather_points(const double* points, const int64_t* offsets, int64_t S, std::vector<double>& pts, std::vector<int64_t>& off) {
+    off.assign((size_t)S + 1, 0);
+    pts.reserve((size_t)offsets[S] * 2);
     for (int64_t s = 0; s < S; ++s) {
         for (int64_t r = offsets[s]; r < offsets[s + 1]; ++r) {
             const double b = points[2 * r], d = points[2 * r + 1];
             if (!std::isfinite(b) || !std::isfinite(d)) continue;  // the essential classes
-            pl.pts.push_back(b);
-            pl.pts.push_back(d);
+            pts.push_back(b);
+            pts.push_back(d);
         }
-        pl.off[s + 1] = (int64_t)(pl.pts.size() / 2);
+        off[s + 1] = (int64_t)(pts.size() / 2);
     }
+}
+
+// pl.pts / off: dgm_gather_points; pl.pairs / P: the P pairs, copied and index-checked or, for pairs == NULL, every i < j in
+// row-major order.  offsets is valid (dgm_check_layout).
+inline int dgm_gather(const double* points, const int64_t* offsets, int64_t S, const int32_t* pairs, int64_t P, PairPlan& pl,
+                      std::string& msg) {
+    pl.P = P;
+    dgm_gather_points(points, offsets, S, pl.pts, pl.off);
     pl.pairs.resize((size_t)P * 2);
     if (pairs) {
         for (int64_t q = 0; q < 2 * P; ++q) {
@@ -131,6 +136,105 @@ inline void dgm_orient(PairPlan& pl, std::vector<uint8_t>& swapped) {
             swapped[p] = 1;
         }
     }
+}
+
+// ---------------------------------------------------------------- the vectorisations (tda_landscape, tda_persistence_image)
+// One plan per call, per diagram and not per pair: the finite points, the diagrams sorted into size
+// classes by their number n of finite points, and for the image the points as (birth, persistence)
+// with their weights.
+
+constexpr int kVecClasses = 4;
+constexpr int kVecClassN[kVecClasses] = {64, 256, 1024, TDA_VEC_MAX_POINTS};  // n at most
+
+struct VecPlan {
+    std::vector<double> pts;     // (total finite, 2): (b, d); after pi_weights (b, pi)
+    std::vector<double> wgt;     // [total finite] the image's weights (pi_weights)
+    std::vector<int64_t> off;    // [S + 1] into pts
+    std::vector<int32_t> order;  // [S]: diagram ids, class 0 first, ascending within a class
+    int64_t cls_cnt[kVecClasses] = {};
+    int cls_n[kVecClasses] = {};  // the largest n of the class
+    int64_t S = 0;
+};
+
+// the layout checks, the finite points and the classes; `what` names the entry in the messages
+inline int vec_gather(const double* points, const int64_t* offsets, int64_t S, const char* what, VecPlan& pl, std::string& msg) {
+    if (S < 0) return msg = "S must be >= 0", TDA_E_INVALID;
+    if (!offsets) return msg = "offsets is NULL", TDA_E_INVALID;
+    if (int rc = dgm_check_layout(points, offsets, S, nullptr, 0, what, msg)) return rc;
+    pl.S = S;
+    dgm_gather_points(points, offsets, S, pl.pts, pl.off);
+    std::vector<uint8_t> cls((size_t)S);
+    for (int64_t s = 0; s < S; ++s) {
+        const int64_t n = pl.off[s + 1] - pl.off[s];
+        if (n > TDA_VEC_MAX_POINTS)
+            return msg = std::string(what) + ": a diagram with more than 4096 finite points is not supported", TDA_E_UNSUPPORTED;
+        int c = 0;
+        while (n > kVecClassN[c]) ++c;
+        cls[s] = (uint8_t)c;
+        pl.cls_cnt[c]++;
+        pl.cls_n[c] = std::max(pl.cls_n[c], (int)n);
+    }
+    pl.order.resize((size_t)S);
+    int64_t at[kVecClasses], sum = 0;
+    for (int c = 0; c < kVecClasses; ++c) {
+        at[c] = sum;
+        sum += pl.cls_cnt[c];
+    }
+    for (int64_t s = 0; s < S; ++s) pl.order[at[cls[s]]++] = (int32_t)s;
+    return 0;
+}
+
+inline int pl_plan(const tda_pl_args* a, VecPlan& pl, std::string& msg) {
+    auto bad = [&](int code, const char* m) { return msg = m, code; };
+    if (!a) return bad(TDA_E_INVALID, "args is NULL");
+    if (a->reserved != 0) return bad(TDA_E_INVALID, "reserved must be 0");
+    if (a->K < 1) return bad(TDA_E_INVALID, "K must be >= 1");
+    if (a->G < 1) return bad(TDA_E_INVALID, "G must be >= 1");
+    if (!a->grid) return bad(TDA_E_INVALID, "grid is NULL");
+    if (a->K > TDA_PL_MAX_DEPTH) return bad(TDA_E_UNSUPPORTED, "landscape: K > 64 is not supported");
+    if (a->G > TDA_PL_MAX_STEPS) return bad(TDA_E_UNSUPPORTED, "landscape: G > 4096 grid values is not supported");
+    for (int32_t g = 0; g < a->G; ++g)
+        if (!std::isfinite(a->grid[g])) return bad(TDA_E_INVALID, "grid holds a non-finite value");
+    if (int rc = vec_gather(a->points, a->offsets, a->S, "landscape", pl, msg)) return rc;
+    if (a->S * ((int64_t)a->K * a->G) > TDA_VEC_MAX_OUT)
+        return bad(TDA_E_UNSUPPORTED, "landscape: S * K * G > 2^24 values in one call is not supported (split the diagrams)");
+    return 0;
+}
+
+// (b, d) -> (b, pi = d - b) in place, and the weights: pi^power for pi > 0 (1 for power 0, pi for power 1), else 0
+inline void pi_weights(VecPlan& pl, double power) {
+    const size_t n = pl.pts.size() / 2;
+    pl.wgt.resize(n);
+    for (size_t p = 0; p < n; ++p) {
+        const double pi = pl.pts[2 * p + 1] - pl.pts[2 * p];
+        pl.pts[2 * p + 1] = pi;
+        pl.wgt[p] = !(pi > 0.0) ? 0.0 : power == 0.0 ? 1.0 : power == 1.0 ? pi : std::pow(pi, power);
+    }
+}
+
+inline int pi_plan(const tda_pi_args* a, VecPlan& pl, std::string& msg) {
+    auto bad = [&](int code, const char* m) { return msg = m, code; };
+    if (!a) return bad(TDA_E_INVALID, "args is NULL");
+    if (a->reserved != 0) return bad(TDA_E_INVALID, "reserved must be 0");
+    if (a->W < 1 || a->H < 1) return bad(TDA_E_INVALID, "W and H must be >= 1");
+    if (!a->x_edges || !a->y_edges) return bad(TDA_E_INVALID, "x_edges or y_edges is NULL");
+    if (!std::isfinite(a->sigma) || !(a->sigma > 0.0)) return bad(TDA_E_INVALID, "sigma must be finite and > 0");
+    if (!std::isfinite(a->weight_power) || a->weight_power < 0.0) return bad(TDA_E_INVALID, "weight_power must be finite and >= 0");
+    if (a->W > TDA_PI_MAX_PIXELS || a->H > TDA_PI_MAX_PIXELS)
+        return bad(TDA_E_UNSUPPORTED, "persistence image: more than 256 pixels per axis is not supported");
+    for (int axis = 0; axis < 2; ++axis) {
+        const double* e = axis ? a->y_edges : a->x_edges;
+        const int32_t n = axis ? a->H : a->W;
+        for (int32_t i = 0; i <= n; ++i)
+            if (!std::isfinite(e[i])) return bad(TDA_E_INVALID, "the edges hold a non-finite value");
+        for (int32_t i = 0; i < n; ++i)
+            if (!(e[i] < e[i + 1])) return bad(TDA_E_INVALID, "the edges must be strictly increasing");
+    }
+    if (int rc = vec_gather(a->points, a->offsets, a->S, "persistence image", pl, msg)) return rc;
+    if (a->S * ((int64_t)a->W * a->H) > TDA_VEC_MAX_OUT)
+        return bad(TDA_E_UNSUPPORTED, "persistence image: S * W * H > 2^24 values in one call is not supported (split the diagrams)");
+    pi_weights(pl, a->weight_power);
+    return 0;
 }
 
 }  // namespace tda

@@ -1667,7 +1667,7 @@ int tda_device_ok(int32_t device) {
 
 }  // extern "C"
 
-#include "aux_ws.h"  // the per-device workspace of the six entries below, and its locking
+#include "aux_ws.h"  // the per-device workspace of the entries below, and its locking
 // UMAP embedding (include/tda_umap.h): same library, same error state
 #include "umap_host.h"
 // effective dimensionality (include/tda_rips.h tda_effective_dim)
@@ -1680,3 +1680,5 @@ int tda_device_ok(int32_t device) {
 #include "bn_host.h"
 // 1-Wasserstein distances between persistence diagrams (include/tda_dgm.h)
 #include "ws_host.h"
+// persistence landscapes and persistence images (include/tda_dgm.h)
+#include "vec_host.h"

@@ -1,4 +1,4 @@
-"""Distances between persistence diagrams on the GPU (include/tda_dgm.h).
+"""Distances between persistence diagrams, and their vectorisations, on the GPU (include/tda_dgm.h).
 
 The reference imports ``persim`` next to ``ripser`` and uses it for
 ``plot_diagrams`` only; comparing the diagrams of a sweep (layer against layer,
@@ -36,6 +36,12 @@ a matched pair paying its Euclidean distance and an unmatched point its L2
 distance to the diagonal (d - b) / sqrt(2).  The solver is exact up to the
 rounding of its float64 duals (tda_dgm.h states the bounds); the matching can
 be returned, and a diagram may hold 512 finite points.
+
+``persistence_landscapes`` and ``persistence_images`` are the two standard
+vectorisations [upstream ``persim.landscapes``, ``persim.PersistenceImager``]:
+one fixed-length vector per diagram, linear in the number of diagrams, no
+matching, up to 4096 finite points per diagram.  The landscape is exact on its
+grid; the image carries a derived error bound (tda_dgm.h).
 """
 from __future__ import annotations
 
@@ -344,3 +350,166 @@ def wasserstein(dgm1, dgm2, matching: bool = False, device: int = 0):
 def sliced_wasserstein_kernel(D, sigma: float):
     """The sliced Wasserstein kernel exp(-D / (2 sigma^2)) (Carriere, Cuturi, Oudot 2017) of distances D."""
     return np.exp(-np.asarray(D, dtype=np.float64) / (2.0 * float(sigma) ** 2))
+
+
+# ---------------------------------------------------------------- vectorisations (tda_landscape, tda_persistence_image)
+def _vec_inputs(dgms, dim: int):
+    """(points, offsets, S) of a landscape or image call, the limit checked and the non-finite
+    points reported."""
+    pts, off = _flatten(dgms, dim)
+    S = len(off) - 1
+    cnt, dropped = _finite_counts(pts, off)
+    if S and cnt.max() > _lib.TDA_VEC_MAX_POINTS:
+        raise NotImplementedError(f"a diagram holds {int(cnt.max())} finite points: more than {_lib.TDA_VEC_MAX_POINTS} is not supported")
+    if dropped:
+        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
+    return pts, off, S
+
+
+def _check_int(name: str, v, hi: int) -> int:
+    if isinstance(v, bool) or int(v) != v:
+        raise ValueError(f"{name} must be an integer")
+    if v < 1:
+        raise ValueError(f"{name} must be >= 1")
+    if v > hi:
+        raise NotImplementedError(f"{name} > {hi} is not supported")
+    return int(v)
+
+
+def _check_out(S: int, F: int):
+    if S * F > _lib.TDA_VEC_MAX_OUT:
+        raise NotImplementedError(f"{S} diagrams of {F} values: more than 2^24 values in one call is not supported (split the diagrams)")
+
+
+def _call_pl(points, offsets, grid, K: int, device: int):
+    """One tda_landscape call: (values (S, K, G), device_ms)."""
+    a = _lib.PlArgs()
+    a.points = points.ctypes.data if len(points) else None
+    a.offsets = offsets.ctypes.data
+    a.S = len(offsets) - 1
+    a.grid, a.G, a.K, a.device = grid.ctypes.data, len(grid), K, int(device)
+    L = _lib.lib()
+    res = ctypes.POINTER(_lib.PlResult)()
+    _lib.check(L.tda_landscape(ctypes.byref(a), ctypes.byref(res)))
+    try:
+        r = res.contents
+        out = np.frombuffer(ctypes.string_at(r.values, r.S * r.F * 8), dtype=np.float64).copy()
+        return out.reshape(r.S, K, len(grid)), float(r.device_ms)
+    finally:
+        L.tda_pl_free(res)
+
+
+def persistence_landscapes(dgms, start=None, stop=None, num_steps: int = 500, depth: int = 10, dim: int = 1, device: int = 0,
+                           return_grid: bool = False, return_time: bool = False):
+    """Persistence landscapes (Bubenik 2015; ``persim.landscapes`` [upstream]) of a list of
+    diagrams, one library call: the (S, depth, num_steps) float64 array of
+    lambda_k(t) = the k-th largest of max(0, min(t - b, d - t)) over a diagram's points, k = 1 ..
+    depth, at t in ``np.linspace(start, stop, num_steps)``.
+
+    dgms: a list of (n, 2) arrays of (birth, death) or of :class:`LayerResult` (then diagram ``dim``
+    of each).  ``start`` / ``stop`` default to the smallest birth / the largest death over all finite
+    points of the call (a call without one needs both given).  This is the exact landscape sampled on
+    the grid, every value one rounded subtraction or +0.0: persim's ``PersLandscapeApprox`` snaps the
+    bars to the grid first and so differs between grid values of a bar's ends.  A diagram's rows are
+    the same bits in any call that holds it.  Points with a non-finite coordinate are ignored, with a
+    warning; a diagram may hold 4096 finite points, depth <= 64, num_steps <= 4096.  With
+    ``return_grid`` also the grid, with ``return_time`` also the call's device time in ms."""
+    K = _check_int("depth", depth, _lib.TDA_PL_MAX_DEPTH)
+    G = _check_int("num_steps", num_steps, _lib.TDA_PL_MAX_STEPS)
+    pts, off, S = _vec_inputs(dgms, dim)
+    fin = pts[np.isfinite(pts).all(axis=1)]
+    if start is None or stop is None:
+        if not len(fin):
+            raise ValueError("no diagram holds a finite point: start and stop must be given")
+        start = float(fin[:, 0].min()) if start is None else start
+        stop = float(fin[:, 1].max()) if stop is None else stop
+    start, stop = float(start), float(stop)
+    if not (np.isfinite(start) and np.isfinite(stop)):
+        raise ValueError("start and stop must be finite")
+    with np.errstate(all="ignore"):
+        grid = np.ascontiguousarray(np.linspace(start, stop, G), dtype=np.float64)
+    if not np.isfinite(grid).all():
+        raise ValueError("start and stop span more than float64 holds")
+    _check_out(S, K * G)
+    out, ms = (np.zeros((0, K, G)), 0.0) if S == 0 else _call_pl(pts, off, grid, K, device)
+    res = (out,) + ((grid,) if return_grid else ()) + ((ms,) if return_time else ())
+    return res if len(res) > 1 else out
+
+
+def persistence_landscape(dgm, start=None, stop=None, num_steps: int = 500, depth: int = 10, device: int = 0, return_grid: bool = False):
+    """The (depth, num_steps) landscape of one (n, 2) diagram (:func:`persistence_landscapes`)."""
+    if isinstance(dgm, LayerResult):
+        raise ValueError("dgm is an (n, 2) array (for LayerResults: persistence_landscapes)")
+    r = persistence_landscapes([dgm], start, stop, num_steps, depth, device=device, return_grid=return_grid)
+    return (r[0][0], r[1]) if return_grid else r[0]
+
+
+def _call_pi(points, offsets, xe, ye, sigma: float, power: float, device: int):
+    """One tda_persistence_image call: (values (S, W, H), device_ms)."""
+    a = _lib.PiArgs()
+    a.points = points.ctypes.data if len(points) else None
+    a.offsets = offsets.ctypes.data
+    a.S = len(offsets) - 1
+    a.x_edges, a.y_edges, a.W, a.H = xe.ctypes.data, ye.ctypes.data, len(xe) - 1, len(ye) - 1
+    a.sigma, a.weight_power, a.device = sigma, power, int(device)
+    L = _lib.lib()
+    res = ctypes.POINTER(_lib.PiResult)()
+    _lib.check(L.tda_persistence_image(ctypes.byref(a), ctypes.byref(res)))
+    try:
+        r = res.contents
+        out = np.frombuffer(ctypes.string_at(r.values, r.S * r.F * 8), dtype=np.float64).copy()
+        return out.reshape(r.S, len(xe) - 1, len(ye) - 1), float(r.device_ms)
+    finally:
+        L.tda_pi_free(res)
+
+
+def _edges(name: str, rng, n: int):
+    try:
+        lo, hi = (float(x) for x in rng)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be a (low, high) pair") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise ValueError(f"{name} must be finite with low < high, got ({lo}, {hi})")
+    with np.errstate(all="ignore"):
+        e = np.ascontiguousarray(np.linspace(lo, hi, n + 1), dtype=np.float64)
+    if not (np.isfinite(e).all() and (np.diff(e) > 0).all()):
+        raise ValueError(f"{name} = ({lo}, {hi}) does not split into {n} pixels of positive width")
+    return e
+
+
+def persistence_images(dgms, birth_range, pers_range, resolution, sigma: float, weight_power: float = 1.0, dim: int = 1,
+                       device: int = 0, return_time: bool = False):
+    """Persistence images (Adams et al. 2017; ``persim.PersistenceImager`` [upstream]) of a list of
+    diagrams, one library call: the (S, nb, npers) float64 array, ``resolution = (nb, npers)`` (or
+    one integer for both), pixel [i, j] covering births ``np.linspace(*birth_range, nb + 1)[i : i + 2]``
+    and persistences ``np.linspace(*pers_range, npers + 1)[j : j + 2]``.
+
+    Every finite point (b, d) becomes (b, d - b), weighted with (d - b) ** weight_power (0 for
+    d <= b) and spread by a Gaussian of standard deviation ``sigma`` in both axes, integrated exactly
+    over each pixel (a difference of two erf per axis).  persim's ``kernel_params["sigma"]`` is the
+    covariance, here ``sigma ** 2`` times the identity, and its default ``skew=True`` (the
+    birth-persistence coordinates) is what is implemented.  Each pixel lies within
+    (2 * 16 + 9 + n) * 2^-53 * sum(weights) of the exact value (tda_dgm.h), and a diagram's image is
+    the same bits in any call that holds it.  dgms, dim, the non-finite points and the 4096-point
+    limit are those of :func:`persistence_landscapes`; at most 256 pixels per axis."""
+    res = (resolution, resolution) if np.ndim(resolution) == 0 else tuple(resolution)
+    if len(res) != 2:
+        raise ValueError("resolution must be an integer or a pair (nb, npers)")
+    W, H = (_check_int("resolution", r, _lib.TDA_PI_MAX_PIXELS) for r in res)
+    sigma, power = float(sigma), float(weight_power)
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"sigma must be finite and > 0, got {sigma}")
+    if not (np.isfinite(power) and power >= 0):
+        raise ValueError(f"weight_power must be finite and >= 0, got {power}")
+    xe, ye = _edges("birth_range", birth_range, W), _edges("pers_range", pers_range, H)
+    pts, off, S = _vec_inputs(dgms, dim)
+    _check_out(S, W * H)
+    out, ms = (np.zeros((0, W, H)), 0.0) if S == 0 else _call_pi(pts, off, xe, ye, sigma, power, device)
+    return (out, ms) if return_time else out
+
+
+def persistence_image(dgm, birth_range, pers_range, resolution, sigma: float, weight_power: float = 1.0, device: int = 0):
+    """The (nb, npers) image of one (n, 2) diagram (:func:`persistence_images`)."""
+    if isinstance(dgm, LayerResult):
+        raise ValueError("dgm is an (n, 2) array (for LayerResults: persistence_images)")
+    return persistence_images([dgm], birth_range, pers_range, resolution, sigma, weight_power, device=device)[0]

@@ -28,7 +28,7 @@ import json
 
 import numpy as np
 
-from .diagrams import bottleneck_matrix, sliced_wasserstein_matrix, wasserstein_matrix
+from .diagrams import bottleneck_matrix, persistence_images, persistence_landscapes, sliced_wasserstein_matrix, wasserstein_matrix
 from .ripser import ripser_batch
 
 
@@ -118,6 +118,25 @@ def layer_distance_matrix(results, dim: int = 1, M: int = 50, device: int = 0, m
     if metric != "sliced_wasserstein":
         raise ValueError(f"metric must be 'sliced_wasserstein', 'bottleneck' or 'wasserstein', got {metric!r}")
     return sliced_wasserstein_matrix(results, M=M, device=device, dim=dim)
+
+
+def layer_features(results, kind: str = "landscape", dim: int = 1, device: int = 0, **kw) -> np.ndarray:
+    """One fixed-length vector per layer from the H_dim diagrams of a sweep: the (L, F)
+    float64 matrix of ``results`` (the second value ``run_sweep`` returns, or a list of
+    (n, 2) arrays) in one GPU call, ready for statistics or a model.  kind "landscape"
+    (diagrams.persistence_landscapes, F = depth * num_steps; pass ``start`` and ``stop``
+    to put every sweep on the same grid) or "image" (diagrams.persistence_images,
+    F = nb * npers; ``birth_range``, ``pers_range``, ``resolution`` and ``sigma`` are
+    required).  ``kw`` goes to that function; each layer's array is flattened row-major."""
+    if kind == "landscape":
+        out = persistence_landscapes(results, dim=dim, device=device, **kw)
+    elif kind == "image":
+        out = persistence_images(results, dim=dim, device=device, **kw)
+    else:
+        raise ValueError(f"kind must be 'landscape' or 'image', got {kind!r}")
+    if isinstance(out, tuple):
+        raise ValueError("layer_features returns the matrix alone: no return_grid / return_time")
+    return out.reshape(len(out), -1)
 
 
 ADVERSARIAL_LABELS = ("img_color", "img_shape", "txt_color", "txt_shape")
