@@ -1,6 +1,6 @@
 /*
- * tda_dgm.h -- distances between persistence diagrams, and their vectorisations
- * (landscapes, images), on the MI355X (gfx950).
+ * tda_dgm.h -- distances between persistence diagrams, their vectorisations
+ * (landscapes, images) and the heat kernel, on the MI355X (gfx950).
  * Part of libtda_rips.so: error codes, tda_last_error() and tda_device_ok()
  * are those of tda_rips.h.  Added to ABI 8 (new symbols only; no existing
  * struct changed).
@@ -162,6 +162,93 @@
  * position in the call and from run to run; the image's sum over p runs in the
  * order of the finite rows whatever the image shape's tiling.  An empty diagram
  * gives +0.0 everywhere.
+ *
+ * tda_heat_kernel: the persistence scale-space kernel (Reininghaus, Huber, Bauer, Kwitt
+ * 2015) of P pairs out of S diagrams in one call, the kernel of every diagram with itself,
+ * and the distance it induces (persim.heat(dgm1, dgm2, sigma) [upstream]).  For diagrams F
+ * (n1 rows) and G (n2 rows), after dropping every row with a non-finite coordinate, and
+ * sigma > 0:
+ *     c8      = 1 / (8 sigma)                       host, one rounded division (8 sigma is exact)
+ *     cn      = 1 / (8 pi sigma)                    host, the rounded constant 8 pi, one product, one division
+ *     r2(p,q) = (b_p - b_q)^2 + (d_p - d_q)^2
+ *     m2(p,q) = (b_p - d_q)^2 + (d_p - b_q)^2       q mirrored at the diagonal
+ *     t(p,q)  = exp(-c8 r2(p,q)) - exp(-c8 m2(p,q))
+ *     k(F,G)  = cn * sum_{p in F} sum_{q in G} t(p,q)
+ *     heat(F,G) = sqrt(max(0, (k(F,F) + k(G,G)) - 2 k(F,G)))      exactly this order of float64 operations
+ * Everything is float64.  r2 and m2 are two rounded subtractions, two rounded products and
+ * one rounded addition each (no fused multiply-add), -c8 r2 is one rounded product.  An
+ * empty diagram gives k = +0.0 against anything, two empty diagrams are at distance 0.0.
+ * It is a kernel in the Hilbert-space sense: the Gram matrix of any list of diagrams is
+ * positive semi-definite up to bound 3 below.
+ *
+ * The result: kern[P] = k of each pair, self[S] = k(F_s, F_s) of every diagram of the call
+ * (the Gram matrix's diagonal), dist[P] = heat, formed on the host from kern and self.
+ *
+ * The order of the sum is a function of (n1, n2) alone.  Every pair is evaluated in one
+ * canonical orientation (the diagram with more finite points is F and, at equal counts, the
+ * one whose point array comes first lexicographically), and then, with R = 64 rows and
+ * Q = 256 columns:
+ *     part[rb][cc] = the rows p = 64 rb .. 64 rb + 63 (a row beyond n1 counts +0.0), each summed
+ *                    over q = 256 cc .. min(256 cc + 255, n2 - 1) in that order, starting from
+ *                    +0.0, then added pairwise over the row index: lanes l and l ^ 1, then
+ *                    l ^ 2, l ^ 4, l ^ 8, l ^ 16, l ^ 32;
+ *     sum          = with the parts numbered k = rb * ceil(n2 / 256) + cc: 64 partial sums, the
+ *                    l-th over k = l, l + 64, ... in that order from +0.0, added pairwise in
+ *                    the same way;
+ *     k            = cn * sum                       one rounded product
+ * whatever the launch shape and whatever else the call holds.
+ *
+ * What is promised, with u = 2^-53:
+ *   1. bit for bit, symmetry and identity: k(F, G) == k(G, F) and heat(F, G) == heat(G, F);
+ *      kern of a pair (s, s) == self[s], and so heat(F, F) is exactly 0.0;
+ *   2. bit for bit, independence of the call: a pair's kern, a diagram's self and so dist are
+ *      the same alone, among other pairs of any sizes, at any position in the pair list,
+ *      with or without an explicit `pairs`, and from run to run;
+ *   3. accuracy: |kern - exact| <= C(n1, n2) u cn, the exact value that of the formulas above
+ *      on the float64 inputs, c8 and cn, n1 >= n2 the pair's two counts, and
+ *          C(n1, n2) = n1 n2 (2 E + 8 + D(n1, n2)),    E = TDA_HK_EXP_ULP = 3,
+ *          D(n1, n2) = min(n2, 256) + 12 + ceil(ceil(n1 / 64) ceil(n2 / 256) / 64);
+ *      self[s] is within C(n, n) u cn.
+ *      Derivation (first order in u; every step rounds up, which covers the u^2 terms):
+ *        a. r2 (and m2): each difference carries a relative error u, its square 3 u, the sum
+ *           of the two non-negative squares 4 u, the product with c8 5 u: the argument
+ *           z = -c8 r2 has a relative error of at most 6 u;
+ *        b. |z| e^z <= 1 / e, so the exponential moves by at most 6 u / e <= 3 u;
+ *        c. the device exp is within E ulp, and an ulp of a value <= 1 is at most u: each
+ *           exponential is within (3 + E) u of the exact one;
+ *        d. a term t is the rounded difference of two such values, |t| <= 1: within
+ *           (2 (3 + E) + 1) u = (2 E + 7) u; the n1 n2 terms together: (2 E + 7) n1 n2 u;
+ *        e. the sum: an addition rounds a partial sum, which is at most the number of terms
+ *           below it, so the additions together err by at most u times the sum, over the
+ *           terms, of the number of additions a term passes through.  That number is at
+ *           most D: min(n2, 256) in its row's chunk, 6 over the rows, ceil(parts / 64) over
+ *           the parts of a lane and 6 over the lanes: D n1 n2 u;
+ *        f. the product with cn rounds a value of at most n1 n2: n1 n2 u.
+ *      E: the ROCm install documents no bound for the device's double exp (no table of ulp
+ *      errors ships with it), so E is the OpenCL conformance bound for double exp, 3 ulp,
+ *      which the device math library is built to meet (as TDA_PI_ERF_ULP was chosen).  C is
+ *      not fitted to observed errors.
+ *      The squared distance q = (k(F,F) + k(G,G)) - 2 k(F,G) before the clamp: within
+ *          B2 = (C(n1, n1) + C(n2, n2) + 2 C(n1, n2)) u cn + 2 u (self_F + self_G + 2 |kern|)
+ *      of the exact one (three bounds of kind 3, the doubling exact, and the two host
+ *      roundings, each of a value of at most self_F + self_G + 2 |kern|).  dist is the correctly
+ *      rounded square root of the clamped value, so |dist - exact| <= sqrt(B2) + u dist.
+ *   4. not promised bit for bit: independence of the order of a diagram's rows.  Two row
+ *      orders agree within bound 3.  What steps a to f derive for them: a term is a function
+ *      of its two points alone, so both orders add the same n1 n2 terms, bit for bit, and
+ *      differ by the roundings of steps e and f only, at most 2 (D + 1) n1 n2 u cn; that is
+ *      below twice bound 3 but, D being at least 14, not below bound 3 itself.  Bound 3 is
+ *      what the tests hold two row orders to, and it is the stricter of the two.
+ *
+ * Limits: at most TDA_HK_MAX_POINTS finite points per diagram, at most TDA_SW_MAX_WORK
+ * diagrams and pairs per call, and at most TDA_SW_MAX_WORK parts (above) over the call's
+ * P + S evaluations (the call's scratch, 8 bytes per part), else TDA_E_UNSUPPORTED.  TDA_E_INVALID, in this order: args NULL,
+ * S < 0, offsets NULL, reserved != 0, sigma not finite, not > 0, or such that c8 or cn is
+ * not a finite normal number, bad offsets, points NULL, P < 0; then TDA_E_UNSUPPORTED for
+ * too many diagrams or pairs, TDA_E_INVALID for a pair index outside [0, S), and
+ * TDA_E_UNSUPPORTED for a diagram beyond the point limit (whether a pair names it or not:
+ * every diagram has a self) and for too many parts.  All argument errors arrive before any
+ * device work.
  */
 #ifndef TDA_DGM_H
 #define TDA_DGM_H
@@ -290,6 +377,31 @@ typedef struct tda_pi_result {
 
 int tda_persistence_image(const tda_pi_args *args, tda_pi_result **out);
 void tda_pi_free(tda_pi_result *r);
+
+#define TDA_HK_MAX_POINTS 4096 /* finite points of one diagram   */
+#define TDA_HK_EXP_ULP 3       /* E of the accuracy bound C(n1, n2) */
+
+typedef struct tda_hk_args {
+    const double *points;   /* host (total, 2) f64 (birth, death); non-finite rows are skipped */
+    const int64_t *offsets; /* host [S + 1] non-decreasing row boundaries, offsets[0] = 0      */
+    int64_t S;              /* diagrams                                                        */
+    const int32_t *pairs;   /* host (P, 2) diagram indices, or NULL: every i < j, row-major    */
+    int64_t P;              /* pairs in `pairs`; ignored when pairs is NULL                    */
+    double sigma;           /* finite, > 0, 1 / (8 sigma) and 1 / (8 pi sigma) finite normal   */
+    int32_t device;         /* HIP device ordinal                                              */
+    int32_t reserved;       /* must be 0                                                       */
+} tda_hk_args;
+
+typedef struct tda_hk_result {
+    int64_t P;          /* pairs computed (S (S - 1) / 2 when pairs was NULL)    */
+    const double *kern; /* host [P]: k of each pair                              */
+    const double *self; /* host [S]: k(F_s, F_s) of every diagram of the call    */
+    const double *dist; /* host [P]: heat of each pair                           */
+    double device_ms;   /* device time of the call (HIP events, copies included) */
+} tda_hk_result;
+
+int tda_heat_kernel(const tda_hk_args *args, tda_hk_result **out);
+void tda_hk_free(tda_hk_result *r);
 
 #ifdef __cplusplus
 }

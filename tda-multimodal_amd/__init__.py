@@ -8,12 +8,12 @@ include/tda_rips.h; no CPU fallback.
 import sys as _sys
 
 from . import diagrams, distributed, metrics, synthetic, umap  # noqa: F401
-from .diagrams import (bottleneck, bottleneck_matrix, persistence_image, persistence_images, persistence_landscape,  # noqa: F401
-                       persistence_landscapes, sliced_wasserstein, sliced_wasserstein_kernel, sliced_wasserstein_matrix, wasserstein,
+from .diagrams import (bottleneck, bottleneck_matrix, heat, heat_kernel_matrix, heat_matrix, persistence_image, persistence_images,  # noqa: F401
+                       persistence_landscape, persistence_landscapes, sliced_wasserstein, sliced_wasserstein_kernel, sliced_wasserstein_matrix, wasserstein,
                        wasserstein_matrix)
 from .metrics import (compute_effective_dimensionality, compute_fixed_window_ed, compute_fixed_window_id,  # noqa: F401
                       compute_intrinsic_dimensionality, matrix_entropy, matrix_entropy_profile)
-from ._lib import BOTTLENECK_EXPORTS, DGM_EXPORTS, EXPORTS, LIB_PATH, VECTOR_EXPORTS, WASSERSTEIN_EXPORTS, build, lib  # noqa: F401
+from ._lib import BOTTLENECK_EXPORTS, DGM_EXPORTS, EXPORTS, HEAT_EXPORTS, LIB_PATH, VECTOR_EXPORTS, WASSERSTEIN_EXPORTS, build, lib  # noqa: F401
 from .pipeline import (get_max_persistence, get_persistence, layer_distance_matrix, layer_features, layer_record,  # noqa: F401
                        layer_record_adversarial, peak_layer, run_adversarial_condition, run_sweep, write_layer_stats,
                        write_summary_stats)
@@ -49,6 +49,9 @@ __all__ = [
     "bottleneck_matrix",
     "wasserstein",
     "wasserstein_matrix",
+    "heat",
+    "heat_matrix",
+    "heat_kernel_matrix",
     "layer_features",
     "persistence_landscape",
     "persistence_landscapes",

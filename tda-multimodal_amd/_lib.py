@@ -316,6 +316,33 @@ TDA_PI_MAX_PIXELS = 256  # per axis
 TDA_PI_ERF_ULP = 16  # E of the image's accuracy bound C(n) = 2 E + 9 + n
 
 
+class HkArgs(ctypes.Structure):  # include/tda_dgm.h tda_hk_args
+    _fields_ = [
+        ("points", ctypes.c_void_p),
+        ("offsets", ctypes.c_void_p),
+        ("S", ctypes.c_int64),
+        ("pairs", ctypes.c_void_p),
+        ("P", ctypes.c_int64),
+        ("sigma", ctypes.c_double),
+        ("device", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class HkResult(ctypes.Structure):  # include/tda_dgm.h tda_hk_result
+    _fields_ = [
+        ("P", ctypes.c_int64),
+        ("kern", ctypes.POINTER(ctypes.c_double)),
+        ("self", ctypes.POINTER(ctypes.c_double)),
+        ("dist", ctypes.POINTER(ctypes.c_double)),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
+TDA_HK_MAX_POINTS = 4096  # finite points of one diagram
+TDA_HK_EXP_ULP = 3  # E of the heat kernel's accuracy bound C(n1, n2)
+
+
 class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
     _fields_ = [
         ("x_train", ctypes.c_void_p),
@@ -356,6 +383,8 @@ BOTTLENECK_EXPORTS = ("tda_bottleneck", "tda_bn_free")
 WASSERSTEIN_EXPORTS = ("tda_wasserstein", "tda_ws_free")
 # the landscape and image symbols of include/tda_dgm.h
 VECTOR_EXPORTS = ("tda_landscape", "tda_pl_free", "tda_persistence_image", "tda_pi_free")
+# the heat kernel symbols of include/tda_dgm.h
+HEAT_EXPORTS = ("tda_heat_kernel", "tda_hk_free")
 
 _lib = None
 
@@ -500,6 +529,10 @@ def lib():
     L.tda_persistence_image.restype = ctypes.c_int
     L.tda_pi_free.argtypes = [ctypes.POINTER(PiResult)]
     L.tda_pi_free.restype = None
+    L.tda_heat_kernel.argtypes = [ctypes.POINTER(HkArgs), ctypes.POINTER(ctypes.POINTER(HkResult))]
+    L.tda_heat_kernel.restype = ctypes.c_int
+    L.tda_hk_free.argtypes = [ctypes.POINTER(HkResult)]
+    L.tda_hk_free.restype = None
     _lib = L
     return L
 

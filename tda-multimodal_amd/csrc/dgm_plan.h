@@ -1,9 +1,9 @@
 // dgm_plan.h -- the host plan of a call of include/tda_dgm.h (tda_sliced_wasserstein, tda_bottleneck,
 // tda_wasserstein): the layout checks, the finite points and the pair list, the pairs sorted into size
-// classes, and (tda_wasserstein) each pair's canonical orientation; and the per-diagram plan of
-// tda_landscape and tda_persistence_image (VecPlan, at the end).
+// classes, and (tda_wasserstein) each pair's canonical orientation; the work list of tda_heat_kernel
+// (HkPlan); and the per-diagram plan of tda_landscape and tda_persistence_image (VecPlan, at the end).
 // Plain C++, no HIP: a function returns an error code and leaves its message in `msg`
-// (tests/dgm_plan_main.cpp runs every case with a host compiler alone).
+// (tests/dgm_plan_main.cpp, hk_plan_main.cpp and vec_plan_main.cpp run every case with a host compiler alone).
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -136,6 +136,69 @@ inline void dgm_orient(PairPlan& pl, std::vector<uint8_t>& swapped) {
             swapped[p] = 1;
         }
     }
+}
+
+// ---------------------------------------------------------------- the heat kernel (tda_heat_kernel)
+// The work list of a call: its P pairs and then the S self pairs (s, s), every one oriented
+// canonically (dgm_orient) and cut into parts of kHkRows rows of the first diagram by kHkChunk
+// columns of the second (tda_dgm.h gives the order of the sum that these two constants fix).
+
+constexpr int kHkRows = 64;     // rows of a part: one per lane of the part's wave
+constexpr int kHkChunk = 256;   // columns of a part: the points staged in LDS
+constexpr int kHkClassN[kPairClasses] = {kHkRows, 512, TDA_HK_MAX_POINTS};  // max(n1, n2) at most
+
+struct HkPlan {
+    PairPlan pl;                    // pl.P = P + S evaluations; pl.pairs oriented
+    std::vector<int64_t> part_off;  // [P + S + 1] into the parts, in the order of pl.pairs
+    int cls_parts[kPairClasses] = {};  // the largest number of parts of an evaluation of the class
+    int64_t P = 0, S = 0;           // the caller's pairs and diagrams
+    double c8 = 0.0, cn = 0.0;
+};
+
+inline int64_t hk_parts(int64_t n1, int64_t n2) { return ((n1 + kHkRows - 1) / kHkRows) * ((n2 + kHkChunk - 1) / kHkChunk); }
+
+inline int hk_plan(const tda_hk_args* a, HkPlan& hp, std::string& msg) {
+    auto bad = [&](int code, const char* m) { return msg = m, code; };
+    if (!a) return bad(TDA_E_INVALID, "args is NULL");
+    if (a->S < 0) return bad(TDA_E_INVALID, "S must be >= 0");
+    if (!a->offsets) return bad(TDA_E_INVALID, "offsets is NULL");
+    if (a->reserved != 0) return bad(TDA_E_INVALID, "reserved must be 0");
+    if (!std::isfinite(a->sigma) || !(a->sigma > 0.0)) return bad(TDA_E_INVALID, "sigma must be finite and > 0");
+    hp.c8 = 1.0 / (8.0 * a->sigma);  // 8 sigma is exact (or overflows: c8 = 0, refused below)
+    hp.cn = 1.0 / (25.132741228718345908 * a->sigma);  // 8 pi, rounded
+    if (!std::isnormal(hp.c8) || !std::isnormal(hp.cn))
+        return bad(TDA_E_INVALID, "sigma: 1 / (8 sigma) and 1 / (8 pi sigma) must be finite normal numbers");
+    if (int rc = dgm_check_layout(a->points, a->offsets, a->S, a->pairs, a->P, "heat kernel", msg)) return rc;
+    const int64_t P = a->pairs ? a->P : a->S * (a->S - 1) / 2;
+    if (P > TDA_SW_MAX_WORK) return bad(TDA_E_UNSUPPORTED, "heat kernel: more than 2^27 pairs in one call is not supported (split the pairs)");
+    PairPlan& pl = hp.pl;
+    if (int rc = dgm_gather(a->points, a->offsets, a->S, a->pairs, P, pl, msg)) return rc;
+    hp.P = P;
+    hp.S = a->S;
+    for (int64_t s = 0; s < a->S; ++s) {  // every diagram has a self, named by a pair or not
+        if (pl.off[s + 1] - pl.off[s] > TDA_HK_MAX_POINTS)
+            return bad(TDA_E_UNSUPPORTED, "heat kernel: a diagram with more than 4096 finite points is not supported");
+        pl.pairs.push_back((int32_t)s);
+        pl.pairs.push_back((int32_t)s);
+    }
+    pl.P = P + a->S;
+    if (int rc = dgm_classify(pl, PairSize::kMax, kHkClassN, "heat kernel: a diagram with more than 4096 finite points is not supported", msg))
+        return rc;
+    std::vector<uint8_t> swapped;
+    dgm_orient(pl, swapped);  // k and heat are symmetric: nothing to turn back
+    hp.part_off.assign((size_t)pl.P + 1, 0);
+    for (int64_t w = 0; w < pl.P; ++w) {
+        const int32_t i = pl.pairs[2 * w], j = pl.pairs[2 * w + 1];
+        const int64_t n1 = pl.off[i + 1] - pl.off[i], n2 = pl.off[j + 1] - pl.off[j];
+        const int64_t parts = hk_parts(n1, n2);
+        hp.part_off[w + 1] = hp.part_off[w] + parts;
+        int c = 0;
+        while (std::max(n1, n2) > kHkClassN[c]) ++c;
+        hp.cls_parts[c] = std::max(hp.cls_parts[c], (int)parts);
+    }
+    if (hp.part_off[pl.P] > TDA_SW_MAX_WORK)
+        return bad(TDA_E_UNSUPPORTED, "heat kernel: more than 2^27 parts of 64 x 256 terms in one call is not supported (split the pairs)");
+    return 0;
 }
 
 // ---------------------------------------------------------------- the vectorisations (tda_landscape, tda_persistence_image)

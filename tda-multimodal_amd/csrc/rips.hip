@@ -1682,3 +1682,5 @@ int tda_device_ok(int32_t device) {
 #include "ws_host.h"
 // persistence landscapes and persistence images (include/tda_dgm.h)
 #include "vec_host.h"
+// the heat (scale-space) kernel between persistence diagrams and its distance (include/tda_dgm.h)
+#include "hk_host.h"

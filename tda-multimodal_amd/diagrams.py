@@ -37,6 +37,13 @@ distance to the diagonal (d - b) / sqrt(2).  The solver is exact up to the
 rounding of its float64 duals (tda_dgm.h states the bounds); the matching can
 be returned, and a diagram may hold 512 finite points.
 
+``heat`` is ``persim.heat(dgm1, dgm2, sigma=0.4)`` [upstream], the distance of the
+persistence scale-space kernel (Reininghaus et al. 2015); ``heat_matrix`` is its
+sweep-level form and ``heat_kernel_matrix`` the kernel's Gram matrix, which is
+positive semi-definite: the one distance here that kernel PCA, an SVM or an MMD
+test can use as it is.  A double sum of exponentials, summed in an order that the
+two point counts alone decide; a diagram may hold 4096 finite points.
+
 ``persistence_landscapes`` and ``persistence_images`` are the two standard
 vectorisations [upstream ``persim.landscapes``, ``persim.PersistenceImager``]:
 one fixed-length vector per diagram, linear in the number of diagrams, no
@@ -350,6 +357,118 @@ def wasserstein(dgm1, dgm2, matching: bool = False, device: int = 0):
 def sliced_wasserstein_kernel(D, sigma: float):
     """The sliced Wasserstein kernel exp(-D / (2 sigma^2)) (Carriere, Cuturi, Oudot 2017) of distances D."""
     return np.exp(-np.asarray(D, dtype=np.float64) / (2.0 * float(sigma) ** 2))
+
+
+# ---------------------------------------------------------------- the heat kernel (tda_heat_kernel)
+_8PI = 25.132741228718345908  # the rounded constant of cn = 1 / (8 pi sigma) (tda_dgm.h)
+
+
+def _check_sigma(sigma) -> float:
+    sigma = float(sigma)
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"sigma must be finite and > 0, got {sigma}")
+    with np.errstate(all="ignore"):
+        c = np.array([1.0 / (np.float64(8.0) * sigma), 1.0 / (np.float64(_8PI) * sigma)])
+    if not (np.isfinite(c).all() and (c >= np.finfo(np.float64).tiny).all()):
+        raise ValueError(f"sigma = {sigma}: 1 / (8 sigma) and 1 / (8 pi sigma) must be finite normal numbers")
+    return sigma
+
+
+def _call_hk(points, offsets, pairs, sigma: float, device: int):
+    """One tda_heat_kernel call: (kern (P,), self (S,), dist (P,), device_ms)."""
+    S = len(offsets) - 1
+    a = _lib.HkArgs()
+    a.points = points.ctypes.data if len(points) else None
+    a.offsets = offsets.ctypes.data
+    a.S = S
+    if pairs is not None:
+        a.pairs, a.P = pairs.ctypes.data, len(pairs)
+    a.sigma, a.device = sigma, int(device)
+    L = _lib.lib()
+    res = ctypes.POINTER(_lib.HkResult)()
+    _lib.check(L.tda_heat_kernel(ctypes.byref(a), ctypes.byref(res)))
+    try:
+        r = res.contents
+        get = lambda p, n: np.frombuffer(ctypes.string_at(p, n * 8), dtype=np.float64).copy() if n else np.zeros(0)  # noqa: E731
+        return get(r.kern, r.P), get(r.self, S), get(r.dist, r.P), float(r.device_ms)
+    finally:
+        L.tda_hk_free(res)
+
+
+def _hk_inputs(dgms, other, dim: int):
+    """(points, offsets, pairs or None, S, S') of a heat kernel call, the limit checked and the
+    non-finite points reported."""
+    pts, off = _flatten(dgms, dim)
+    S = S2 = len(off) - 1
+    pairs = None
+    if other is not None:
+        pts2, off2 = _flatten(other, dim)
+        S2 = len(off2) - 1
+        pts, off = np.concatenate([pts, pts2]), np.concatenate([off, off[-1] + off2[1:]])
+        pairs = np.stack(np.meshgrid(np.arange(S), S + np.arange(S2), indexing="ij"), -1).reshape(-1, 2).astype(np.int32)
+    cnt, dropped = _finite_counts(pts, off)
+    if len(cnt) and cnt.max() > _lib.TDA_HK_MAX_POINTS:
+        raise NotImplementedError(f"a diagram holds {int(cnt.max())} finite points: more than {_lib.TDA_HK_MAX_POINTS} is not supported")
+    if dropped:
+        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
+    return pts, off, pairs, S, S2
+
+
+def _hk_matrix(dgms, sigma, other, device: int, dim: int, want_kernel: bool):
+    sigma = _check_sigma(sigma)
+    pts, off, pairs, S, S2 = _hk_inputs(dgms, other, dim)
+    if other is None:
+        # the distances of fewer than two diagrams and the Gram matrix of none: nothing to launch
+        if S == 0 or (S == 1 and not want_kernel):
+            return np.zeros((S, S)), 0.0
+        kern, self_, dist, ms = _call_hk(pts, off, None, sigma, device)
+        D = np.zeros((S, S))
+        D[np.triu_indices(S, 1)] = kern if want_kernel else dist  # row-major i < j: the order of the library's all-pairs result
+        D = D + D.T
+        if want_kernel:
+            D[np.diag_indices(S)] = self_
+        return D, ms
+    if S == 0 or S2 == 0:
+        return np.zeros((S, S2)), 0.0
+    kern, _, dist, ms = _call_hk(pts, off, pairs, sigma, device)
+    return (kern if want_kernel else dist).reshape(S, S2), ms
+
+
+def heat_matrix(dgms, sigma: float = 0.4, other=None, device: int = 0, dim: int = 1, return_time: bool = False):
+    """Heat kernel distances between every pair of diagrams, one library call.
+
+    The arguments and the result are those of :func:`bottleneck_matrix`, with the
+    kernel's scale ``sigma``: the (S, S) matrix is symmetric with an exactly zero
+    diagonal, the (S, S') matrix is ``dgms`` against ``other``.  A diagram may hold
+    4096 finite points.  A value is the same bits in any call that holds the pair,
+    in either orientation; tda_dgm.h derives its error bound."""
+    D, ms = _hk_matrix(dgms, sigma, other, device, dim, False)
+    return (D, ms) if return_time else D
+
+
+def heat_kernel_matrix(dgms, sigma: float = 0.4, other=None, device: int = 0, dim: int = 1, return_time: bool = False):
+    """The Gram matrix of the persistence scale-space kernel (Reininghaus et al. 2015),
+
+        k(F, G) = 1 / (8 pi sigma) * sum_{p in F, q in G} exp(-|p - q|^2 / (8 sigma)) - exp(-|p - q'|^2 / (8 sigma)),
+
+    q' the mirror image (d, b) of q: (S, S) and symmetric, with k(F, F) on its diagonal, or
+    (S, S') with ``other``.  It is positive semi-definite up to the rounding bound of
+    tda_dgm.h, so it can go into kernel PCA, an SVM or an MMD test as it is.  The arguments
+    are those of :func:`heat_matrix`, whose values are sqrt(k(F, F) + k(G, G) - 2 k(F, G)).
+    The library evaluates k(F, F) of every diagram of a call; with ``other`` this function does not
+    return them, so a block of few large diagrams costs up to twice its own terms."""
+    K, ms = _hk_matrix(dgms, sigma, other, device, dim, True)
+    return (K, ms) if return_time else K
+
+
+def heat(dgm1, dgm2, sigma: float = 0.4, device: int = 0) -> float:
+    """``persim.heat(dgm1, dgm2, sigma=0.4)`` [upstream] on the GPU: the distance the
+    persistence scale-space kernel induces between two (n, 2) diagrams.  Points with a
+    non-finite coordinate are ignored, with a warning."""
+    for d in (dgm1, dgm2):
+        if isinstance(d, LayerResult):
+            raise ValueError("dgm1 and dgm2 are (n, 2) arrays (for LayerResults: heat_matrix)")
+    return float(heat_matrix([dgm1], sigma, other=[dgm2], device=device)[0, 0])
 
 
 # ---------------------------------------------------------------- vectorisations (tda_landscape, tda_persistence_image)

@@ -28,7 +28,7 @@ import json
 
 import numpy as np
 
-from .diagrams import bottleneck_matrix, persistence_images, persistence_landscapes, sliced_wasserstein_matrix, wasserstein_matrix
+from .diagrams import bottleneck_matrix, heat_matrix, persistence_images, persistence_landscapes, sliced_wasserstein_matrix, wasserstein_matrix
 from .ripser import ripser_batch
 
 
@@ -100,23 +100,28 @@ def run_sweep(clouds, maxdim: int = 1, thresh: float = np.inf, layer_ids=None, d
     return recs, res
 
 
-def layer_distance_matrix(results, dim: int = 1, M: int = 50, device: int = 0, metric: str = "sliced_wasserstein") -> np.ndarray:
+def layer_distance_matrix(results, dim: int = 1, M: int = 50, device: int = 0, metric: str = "sliced_wasserstein",
+                          sigma: float = 0.4) -> np.ndarray:
     """Distances between the H_dim diagrams of a sweep's layers: the (L, L) float64
     matrix (symmetric, zero diagonal) of ``results``, the second value ``run_sweep``
     returns, in one GPU call.  metric "sliced_wasserstein" (the default, over M
     directions: diagrams.sliced_wasserstein_matrix), "bottleneck" (exact, M is
     ignored: diagrams.bottleneck_matrix; in the units of ``max_h1_persistence``, a
-    layer's distance to an empty diagram being half of it) or "wasserstein" (the
+    layer's distance to an empty diagram being half of it), "wasserstein" (the
     optimal-transport distance in which every bar counts, M is ignored:
-    diagrams.wasserstein_matrix).  Layers of equal
+    diagrams.wasserstein_matrix) or "heat" (the distance of the persistence
+    scale-space kernel at scale ``sigma``, which only this metric reads; M is
+    ignored: diagrams.heat_matrix).  Layers of equal
     ``max_h1_persistence`` can hold quite different diagrams; this is the
     layer-against-layer view the per-layer records cannot give."""
     if metric == "bottleneck":
         return bottleneck_matrix(results, device=device, dim=dim)
     if metric == "wasserstein":
         return wasserstein_matrix(results, device=device, dim=dim)
+    if metric == "heat":
+        return heat_matrix(results, sigma=sigma, device=device, dim=dim)
     if metric != "sliced_wasserstein":
-        raise ValueError(f"metric must be 'sliced_wasserstein', 'bottleneck' or 'wasserstein', got {metric!r}")
+        raise ValueError(f"metric must be 'sliced_wasserstein', 'bottleneck', 'wasserstein' or 'heat', got {metric!r}")
     return sliced_wasserstein_matrix(results, M=M, device=device, dim=dim)
 
 
