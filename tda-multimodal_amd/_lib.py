@@ -375,16 +375,22 @@ class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
 EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "tda_version", "tda_device_ok",
            "tda_effective_dim", "tda_effective_dim_windows", "tda_matrix_entropy", "tda_greedy_perm", "tda_greedy_free",
            "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan")
-# the sliced Wasserstein symbols of include/tda_dgm.h; the header's later additions have tuples of their own
-DGM_EXPORTS = ("tda_sliced_wasserstein", "tda_sw_free")
-# the bottleneck symbols of include/tda_dgm.h
-BOTTLENECK_EXPORTS = ("tda_bottleneck", "tda_bn_free")
-# the Wasserstein symbols of include/tda_dgm.h
-WASSERSTEIN_EXPORTS = ("tda_wasserstein", "tda_ws_free")
-# the landscape and image symbols of include/tda_dgm.h
-VECTOR_EXPORTS = ("tda_landscape", "tda_pl_free", "tda_persistence_image", "tda_pi_free")
-# the heat kernel symbols of include/tda_dgm.h
-HEAT_EXPORTS = ("tda_heat_kernel", "tda_hk_free")
+# the entries of include/tda_dgm.h, all of one shape, int entry(const args*, result**) and void free(result*):
+# name -> (entry symbol, free symbol, args struct, result struct)
+DGM_ENTRIES = {
+    "sw": ("tda_sliced_wasserstein", "tda_sw_free", SwArgs, SwResult),
+    "bn": ("tda_bottleneck", "tda_bn_free", BnArgs, BnResult),
+    "ws": ("tda_wasserstein", "tda_ws_free", WsArgs, WsResult),
+    "pl": ("tda_landscape", "tda_pl_free", PlArgs, PlResult),
+    "pi": ("tda_persistence_image", "tda_pi_free", PiArgs, PiResult),
+    "hk": ("tda_heat_kernel", "tda_hk_free", HkArgs, HkResult),
+}
+# their symbols, one tuple per addition to the header
+DGM_EXPORTS = DGM_ENTRIES["sw"][:2]
+BOTTLENECK_EXPORTS = DGM_ENTRIES["bn"][:2]
+WASSERSTEIN_EXPORTS = DGM_ENTRIES["ws"][:2]
+VECTOR_EXPORTS = DGM_ENTRIES["pl"][:2] + DGM_ENTRIES["pi"][:2]
+HEAT_EXPORTS = DGM_ENTRIES["hk"][:2]
 
 _lib = None
 
@@ -509,30 +515,11 @@ def lib():
     L.tda_greedy_free.restype = None
     L.tda_umap_transform.argtypes = [ctypes.POINTER(UmapTransformArgs)]
     L.tda_umap_transform.restype = ctypes.c_int
-    L.tda_sliced_wasserstein.argtypes = [ctypes.POINTER(SwArgs), ctypes.POINTER(ctypes.POINTER(SwResult))]
-    L.tda_sliced_wasserstein.restype = ctypes.c_int
-    L.tda_sw_free.argtypes = [ctypes.POINTER(SwResult)]
-    L.tda_sw_free.restype = None
-    L.tda_bottleneck.argtypes = [ctypes.POINTER(BnArgs), ctypes.POINTER(ctypes.POINTER(BnResult))]
-    L.tda_bottleneck.restype = ctypes.c_int
-    L.tda_bn_free.argtypes = [ctypes.POINTER(BnResult)]
-    L.tda_bn_free.restype = None
-    L.tda_wasserstein.argtypes = [ctypes.POINTER(WsArgs), ctypes.POINTER(ctypes.POINTER(WsResult))]
-    L.tda_wasserstein.restype = ctypes.c_int
-    L.tda_ws_free.argtypes = [ctypes.POINTER(WsResult)]
-    L.tda_ws_free.restype = None
-    L.tda_landscape.argtypes = [ctypes.POINTER(PlArgs), ctypes.POINTER(ctypes.POINTER(PlResult))]
-    L.tda_landscape.restype = ctypes.c_int
-    L.tda_pl_free.argtypes = [ctypes.POINTER(PlResult)]
-    L.tda_pl_free.restype = None
-    L.tda_persistence_image.argtypes = [ctypes.POINTER(PiArgs), ctypes.POINTER(ctypes.POINTER(PiResult))]
-    L.tda_persistence_image.restype = ctypes.c_int
-    L.tda_pi_free.argtypes = [ctypes.POINTER(PiResult)]
-    L.tda_pi_free.restype = None
-    L.tda_heat_kernel.argtypes = [ctypes.POINTER(HkArgs), ctypes.POINTER(ctypes.POINTER(HkResult))]
-    L.tda_heat_kernel.restype = ctypes.c_int
-    L.tda_hk_free.argtypes = [ctypes.POINTER(HkResult)]
-    L.tda_hk_free.restype = None
+    for entry, free, Args, Result in DGM_ENTRIES.values():
+        getattr(L, entry).argtypes = [ctypes.POINTER(Args), ctypes.POINTER(ctypes.POINTER(Result))]
+        getattr(L, entry).restype = ctypes.c_int
+        getattr(L, free).argtypes = [ctypes.POINTER(Result)]
+        getattr(L, free).restype = None
     _lib = L
     return L
 

@@ -1,6 +1,6 @@
 // aux_ws.h -- the per-device workspace of the entries beside the persistence pipeline (UMAP, the
-// spectral metrics, greedy landmarks, the three diagram distances, landscapes, images and the heat kernel), part of rips.hip's translation
-// unit.  Each entry has a stream, buffers and a mutex of its own: no slot's stream is used and
+// spectral metrics, greedy landmarks and the six diagram entries, which use it through dgm_call.h),
+// part of rips.hip's translation unit.  Each entry has a stream, buffers and a mutex of its own: no slot's stream is used and
 // nothing is captured into a graph.  The rules these entries share with the pipeline live here:
 // every allocation and free runs under g_capture_mu (never beside a slot's graph capture), a failed
 // growth leaves an empty buffer, and hipFuncSetAttribute runs once per workspace under g_attr_mu.

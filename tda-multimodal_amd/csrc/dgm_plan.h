@@ -1,9 +1,10 @@
-// dgm_plan.h -- the host plan of a call of include/tda_dgm.h (tda_sliced_wasserstein, tda_bottleneck,
-// tda_wasserstein): the layout checks, the finite points and the pair list, the pairs sorted into size
-// classes, and (tda_wasserstein) each pair's canonical orientation; the work list of tda_heat_kernel
-// (HkPlan); and the per-diagram plan of tda_landscape and tda_persistence_image (VecPlan, at the end).
-// Plain C++, no HIP: a function returns an error code and leaves its message in `msg`
-// (tests/dgm_plan_main.cpp, hk_plan_main.cpp and vec_plan_main.cpp run every case with a host compiler alone).
+// dgm_plan.h -- the host plans of the six entries of include/tda_dgm.h, one per entry: sw_plan, bn_plan
+// and ws_plan (PairPlan: the layout checks, the finite points and the pair list, the pairs sorted into size
+// classes and, for tda_wasserstein, oriented canonically), hk_plan (HkPlan: the work list of
+// tda_heat_kernel) and pl_plan / pi_plan (VecPlan: per diagram, at the end), each with the size classes
+// of its launches.  Plain C++, no HIP: a plan returns an error code and leaves its message in `msg`
+// (tests/dgm_plan_main.cpp, ws_plan_main.cpp, hk_plan_main.cpp and vec_plan_main.cpp run them with a
+// host compiler alone).  The checks of a plan run in the order its entry has always made them.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -28,6 +29,15 @@ struct PairPlan {
     int cls_n[kPairClasses] = {};  // the largest size of the class
     int64_t P = 0;
 };
+
+// the first three checks of a pair entry, before its own (M, reserved, flags, sigma)
+template <typename Args>
+inline int dgm_check_head(const Args* a, std::string& msg) {
+    if (!a) return msg = "args is NULL", TDA_E_INVALID;
+    if (a->S < 0) return msg = "S must be >= 0", TDA_E_INVALID;
+    if (!a->offsets) return msg = "offsets is NULL", TDA_E_INVALID;
+    return 0;
+}
 
 // The layout checks every entry of tda_dgm.h shares, in the order tda_sliced_wasserstein has always made them
 // (S >= 0 and offsets != NULL are checked by the caller first, with its own checks in between).
@@ -81,30 +91,53 @@ inline int dgm_gather(const double* points, const int64_t* offsets, int64_t S, c
     return 0;
 }
 
+// What a pair entry does after its own argument checks: the layout, P (every i < j without a list),
+// the limit of a call's work (P and P * per_pair at most 2^27, else `too_many`), the points and the pairs.
+template <typename Args>
+inline int dgm_pairs(const Args* a, const char* what, int64_t per_pair, const char* too_many, PairPlan& pl, std::string& msg) {
+    if (int rc = dgm_check_layout(a->points, a->offsets, a->S, a->pairs, a->P, what, msg)) return rc;
+    const int64_t P = a->pairs ? a->P : a->S * (a->S - 1) / 2;
+    if (P > TDA_SW_MAX_WORK || P * per_pair > TDA_SW_MAX_WORK) return msg = too_many, TDA_E_UNSUPPORTED;
+    return dgm_gather(a->points, a->offsets, a->S, a->pairs, P, pl, msg);
+}
+
+// The counting sort of every plan: item x of size size_of(x) belongs to the first class whose limit
+// holds it (limits ascending); order lists the items class 0 first, ascending within a class, and
+// cls_n is the largest size of each class.  False at the first item larger than the last limit.
+template <int C, typename SizeOf>
+inline bool dgm_sort_classes(int64_t count, SizeOf&& size_of, const int (&limits)[C], std::vector<int32_t>& order, int64_t (&cls_cnt)[C],
+                             int (&cls_n)[C]) {
+    std::vector<uint8_t> cls((size_t)count);
+    for (int64_t x = 0; x < count; ++x) {
+        const int64_t n = size_of(x);
+        if (n > limits[C - 1]) return false;
+        int c = 0;
+        while (n > limits[c]) ++c;
+        cls[x] = (uint8_t)c;
+        cls_cnt[c]++;
+        cls_n[c] = std::max(cls_n[c], (int)n);
+    }
+    order.resize((size_t)count);
+    int64_t at[C], sum = 0;
+    for (int c = 0; c < C; ++c) {
+        at[c] = sum;
+        sum += cls_cnt[c];
+    }
+    for (int64_t x = 0; x < count; ++x) order[at[cls[x]]++] = (int32_t)x;
+    return true;
+}
+
 enum class PairSize { kSum, kMax };  // a pair's size: n1 + n2 or max(n1, n2) finite points
 
 // Sorts the gathered pairs into classes: class c holds the pairs of size <= limits[c] (ascending;
 // the last one is the limit of a call: a larger pair is TDA_E_UNSUPPORTED with `too_large`).
 inline int dgm_classify(PairPlan& pl, PairSize measure, const int (&limits)[kPairClasses], const char* too_large, std::string& msg) {
-    std::vector<uint8_t> cls((size_t)pl.P);
-    for (int64_t p = 0; p < pl.P; ++p) {
+    auto size_of = [&](int64_t p) {
         const int32_t i = pl.pairs[2 * p], j = pl.pairs[2 * p + 1];
         const int64_t n1 = pl.off[i + 1] - pl.off[i], n2 = pl.off[j + 1] - pl.off[j];
-        const int64_t n = measure == PairSize::kSum ? n1 + n2 : std::max(n1, n2);
-        if (n > limits[kPairClasses - 1]) return msg = too_large, TDA_E_UNSUPPORTED;
-        int c = 0;
-        while (n > limits[c]) ++c;
-        cls[p] = (uint8_t)c;
-        pl.cls_cnt[c]++;
-        pl.cls_n[c] = std::max(pl.cls_n[c], (int)n);
-    }
-    pl.order.resize((size_t)pl.P);
-    int64_t at[kPairClasses], sum = 0;
-    for (int c = 0; c < kPairClasses; ++c) {
-        at[c] = sum;
-        sum += pl.cls_cnt[c];
-    }
-    for (int64_t p = 0; p < pl.P; ++p) pl.order[at[cls[p]]++] = (int32_t)p;
+        return measure == PairSize::kSum ? n1 + n2 : std::max(n1, n2);
+    };
+    if (!dgm_sort_classes(pl.P, size_of, limits, pl.order, pl.cls_cnt, pl.cls_n)) return msg = too_large, TDA_E_UNSUPPORTED;
     return 0;
 }
 
@@ -138,6 +171,59 @@ inline void dgm_orient(PairPlan& pl, std::vector<uint8_t>& swapped) {
     }
 }
 
+// ---------------------------------------------------------------- the three distances
+// Size classes: what a class means for a launch is told where the launch is (dgm_host.h, bn_host.h, ws_host.h).
+
+struct SwClass {
+    int npow_max, threads, dirs_per_wg;  // next_pow2(n1 + n2) at most
+};
+constexpr SwClass kSwClasses[kPairClasses] = {{128, 64, 8}, {1024, 256, 1}, {TDA_SW_MAX_POINTS, 1024, 1}};
+constexpr int kBnClassN[kPairClasses] = {64, 256, TDA_BN_MAX_POINTS};  // max(n1, n2) at most; also the workgroup size
+constexpr int kWsClassN[kPairClasses] = {64, 256, TDA_WS_MAX_POINTS};  // max(n1, n2) at most; also the workgroup size
+
+inline int sw_plan(const tda_sw_args* a, PairPlan& pl, std::string& msg) {
+    auto bad = [&](int code, const char* m) { return msg = m, code; };
+    if (int rc = dgm_check_head(a, msg)) return rc;
+    if (a->M < 1) return bad(TDA_E_INVALID, "M must be >= 1");
+    if (a->M > TDA_SW_MAX_DIRECTIONS) return bad(TDA_E_UNSUPPORTED, "sliced Wasserstein: M > 1024 directions is not supported");
+    if (int rc = dgm_pairs(a, "sliced Wasserstein", a->M, "sliced Wasserstein: P * M > 2^27 in one call is not supported (split the pairs)", pl, msg))
+        return rc;
+    const int limits[kPairClasses] = {kSwClasses[0].npow_max, kSwClasses[1].npow_max, kSwClasses[2].npow_max};
+    return dgm_classify(pl, PairSize::kSum, limits, "sliced Wasserstein: a pair of diagrams with more than 4096 finite points together is not supported",
+                        msg);
+}
+
+inline int bn_plan(const tda_bn_args* a, PairPlan& pl, std::string& msg) {
+    if (int rc = dgm_check_head(a, msg)) return rc;
+    if (a->reserved != 0) return msg = "reserved must be 0", TDA_E_INVALID;
+    if (int rc = dgm_pairs(a, "bottleneck", 1, "bottleneck: more than 2^27 pairs in one call is not supported (split the pairs)", pl, msg)) return rc;
+    return dgm_classify(pl, PairSize::kMax, kBnClassN, "bottleneck: a diagram with more than 512 finite points is not supported", msg);
+}
+
+// the pairs oriented (swapped[p]: pair p was exchanged) and, with the matching, moff [P + 1]: where
+// the mates of each pair's first diagram (as oriented) start in the device's match array
+struct WsPlan {
+    PairPlan pl;
+    std::vector<uint8_t> swapped;
+    std::vector<int64_t> moff;
+};
+
+inline int ws_plan(const tda_ws_args* a, WsPlan& wp, std::string& msg) {
+    if (int rc = dgm_check_head(a, msg)) return rc;
+    if (a->flags & ~TDA_WS_WANT_MATCHING) return msg = "flags holds an unknown bit", TDA_E_INVALID;
+    PairPlan& pl = wp.pl;
+    if (int rc = dgm_pairs(a, "wasserstein", 1, "wasserstein: more than 2^27 pairs in one call is not supported (split the pairs)", pl, msg)) return rc;
+    if (int rc = dgm_classify(pl, PairSize::kMax, kWsClassN, "wasserstein: a diagram with more than 512 finite points is not supported", msg)) return rc;
+    dgm_orient(pl, wp.swapped);
+    if (a->flags & TDA_WS_WANT_MATCHING) {
+        wp.moff.assign((size_t)pl.P + 1, 0);
+        for (int64_t p = 0; p < pl.P; ++p) wp.moff[p + 1] = wp.moff[p] + (pl.off[pl.pairs[2 * p] + 1] - pl.off[pl.pairs[2 * p]]);
+        if (wp.moff[pl.P] > TDA_SW_MAX_WORK)
+            return msg = "wasserstein: a matching of more than 2^27 entries in one call is not supported (split the pairs)", TDA_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
 // ---------------------------------------------------------------- the heat kernel (tda_heat_kernel)
 // The work list of a call: its P pairs and then the S self pairs (s, s), every one oriented
 // canonically (dgm_orient) and cut into parts of kHkRows rows of the first diagram by kHkChunk
@@ -159,21 +245,16 @@ inline int64_t hk_parts(int64_t n1, int64_t n2) { return ((n1 + kHkRows - 1) / k
 
 inline int hk_plan(const tda_hk_args* a, HkPlan& hp, std::string& msg) {
     auto bad = [&](int code, const char* m) { return msg = m, code; };
-    if (!a) return bad(TDA_E_INVALID, "args is NULL");
-    if (a->S < 0) return bad(TDA_E_INVALID, "S must be >= 0");
-    if (!a->offsets) return bad(TDA_E_INVALID, "offsets is NULL");
+    if (int rc = dgm_check_head(a, msg)) return rc;
     if (a->reserved != 0) return bad(TDA_E_INVALID, "reserved must be 0");
     if (!std::isfinite(a->sigma) || !(a->sigma > 0.0)) return bad(TDA_E_INVALID, "sigma must be finite and > 0");
     hp.c8 = 1.0 / (8.0 * a->sigma);  // 8 sigma is exact (or overflows: c8 = 0, refused below)
     hp.cn = 1.0 / (25.132741228718345908 * a->sigma);  // 8 pi, rounded
     if (!std::isnormal(hp.c8) || !std::isnormal(hp.cn))
         return bad(TDA_E_INVALID, "sigma: 1 / (8 sigma) and 1 / (8 pi sigma) must be finite normal numbers");
-    if (int rc = dgm_check_layout(a->points, a->offsets, a->S, a->pairs, a->P, "heat kernel", msg)) return rc;
-    const int64_t P = a->pairs ? a->P : a->S * (a->S - 1) / 2;
-    if (P > TDA_SW_MAX_WORK) return bad(TDA_E_UNSUPPORTED, "heat kernel: more than 2^27 pairs in one call is not supported (split the pairs)");
     PairPlan& pl = hp.pl;
-    if (int rc = dgm_gather(a->points, a->offsets, a->S, a->pairs, P, pl, msg)) return rc;
-    hp.P = P;
+    if (int rc = dgm_pairs(a, "heat kernel", 1, "heat kernel: more than 2^27 pairs in one call is not supported (split the pairs)", pl, msg)) return rc;
+    const int64_t P = hp.P = pl.P;
     hp.S = a->S;
     for (int64_t s = 0; s < a->S; ++s) {  // every diagram has a self, named by a pair or not
         if (pl.off[s + 1] - pl.off[s] > TDA_HK_MAX_POINTS)
@@ -226,24 +307,8 @@ inline int vec_gather(const double* points, const int64_t* offsets, int64_t S, c
     if (int rc = dgm_check_layout(points, offsets, S, nullptr, 0, what, msg)) return rc;
     pl.S = S;
     dgm_gather_points(points, offsets, S, pl.pts, pl.off);
-    std::vector<uint8_t> cls((size_t)S);
-    for (int64_t s = 0; s < S; ++s) {
-        const int64_t n = pl.off[s + 1] - pl.off[s];
-        if (n > TDA_VEC_MAX_POINTS)
-            return msg = std::string(what) + ": a diagram with more than 4096 finite points is not supported", TDA_E_UNSUPPORTED;
-        int c = 0;
-        while (n > kVecClassN[c]) ++c;
-        cls[s] = (uint8_t)c;
-        pl.cls_cnt[c]++;
-        pl.cls_n[c] = std::max(pl.cls_n[c], (int)n);
-    }
-    pl.order.resize((size_t)S);
-    int64_t at[kVecClasses], sum = 0;
-    for (int c = 0; c < kVecClasses; ++c) {
-        at[c] = sum;
-        sum += pl.cls_cnt[c];
-    }
-    for (int64_t s = 0; s < S; ++s) pl.order[at[cls[s]]++] = (int32_t)s;
+    if (!dgm_sort_classes(S, [&](int64_t s) { return pl.off[s + 1] - pl.off[s]; }, kVecClassN, pl.order, pl.cls_cnt, pl.cls_n))
+        return msg = std::string(what) + ": a diagram with more than 4096 finite points is not supported", TDA_E_UNSUPPORTED;
     return 0;
 }
 

@@ -1,12 +1,12 @@
 // hk_host.h -- host side of tda_heat_kernel (include/tda_dgm.h), part of rips.hip's
 // translation unit (shares its error state and device checks; the plan is dgm_plan.h's
-// HkPlan, the upload's layout dgm_host.h's, the workspace aux_ws.h's).
+// HkPlan, the frame of the call dgm_call.h's).
 //
 // One call, the shape of the distance entries: drop the non-finite points on the host, add
 // the S self pairs to the P pairs, orient every evaluation canonically and sort them into
 // size classes, upload everything in one copy, launch k_hk_parts once per non-empty class
-// and k_hk_sum once (each in slices of 2^24 evaluations, the launch's grid limit), copy the P + S kernel values back in one copy, and form the distances
-// on the host.
+// and k_hk_sum once (each in slices of 2^24 evaluations, the launch's grid limit), copy the
+// P + S kernel values back in one copy, and form the distances on the host.
 //
 // Size classes (the larger count of an evaluation): <= 64 (one part), <= 512 (at most 16),
 // <= 4096 (at most 1024).  A class's grid is (its evaluations, the parts of its largest
@@ -19,6 +19,7 @@
 // The parts (8 bytes each, at most 2^27 per call) live in the workspace buffer.
 #pragma once
 #include "../../include/tda_dgm.h"
+#include "dgm_call.h"
 #include "hk_kernels.h"
 
 namespace {
@@ -47,32 +48,19 @@ extern "C" int tda_heat_kernel(const tda_hk_args* a, tda_hk_result** out) {
     R->kern.assign(std::max<size_t>(W, 1), 0.0);
     R->dist.assign(std::max<size_t>(P, 1), 0.0);
     R->pub.P = hp.P;
-    if (W == 0) {  // no diagram: nothing to launch
-        R->pub.kern = R->pub.self = R->kern.data();
-        R->pub.dist = R->dist.data();
-        *out = &R.release()->pub;
-        return 0;
-    }
+    R->pub.kern = R->kern.data();
+    R->pub.self = R->kern.data() + P;
+    R->pub.dist = R->dist.data();
+    if (W == 0) return dgm_return(R, out);  // no diagram: nothing to launch
 
-    Carve cv;
-    const PlanAt at(pl, cv);
-    const size_t o_poff = cv.take(hp.part_off.size() * 8);
-    const size_t up_bytes = cv.o;  // the uploaded part
-    const size_t o_part = cv.take((size_t)hp.part_off[W] * 8), o_kern = cv.take(W * 8);
-    std::vector<char> up(up_bytes);
-    at.pack(pl, up.data());
-    std::memcpy(up.data() + o_poff, hp.part_off.data(), hp.part_off.size() * 8);
-
-    AuxWs& w = aux_ws(kAuxHk, a->device);
-    std::lock_guard<std::mutex> guard(w.mu);
-    if (int rc = aux_open(w, 2)) return rc;
-    if (int rc = aux_reserve(w, cv.o)) return rc;
-    hipStream_t s = w.stream;
-    const int64_t* poff = (const int64_t*)(w.buf + o_poff);
-    double* part = (double*)(w.buf + o_part);
-    double* kern = (double*)(w.buf + o_kern);
-    HIPC(hipEventRecord(w.ev[0], s));
-    HIPC(hipMemcpyAsync(w.buf, up.data(), up_bytes, hipMemcpyHostToDevice, s));
+    DgmCall call;
+    const PairAt at(call, pl);
+    const size_t o_poff = call.upload(hp.part_off);
+    const size_t o_part = call.device((size_t)hp.part_off[W] * 8), o_kern = call.device(W * 8);
+    if (int rc = call.begin(kAuxHk, a->device)) return rc;
+    hipStream_t s = call.stream();
+    const int64_t* poff = call.at<const int64_t>(o_poff);
+    double* part = call.at<double>(o_part);
     // a launch's grid x times its block size has to stay below 2^32 threads: at most kHkGridX evaluations per launch
     int64_t first = 0;
     for (int c = 0; c < kPairClasses; ++c) {
@@ -80,8 +68,8 @@ extern "C" int tda_heat_kernel(const tda_hk_args* a, tda_hk_result** out) {
         if (hp.cls_parts[c])  // a class of empty evaluations has nothing to add up
             for (int64_t at0 = 0; at0 < cnt; at0 += kHkGridX) {
                 hipLaunchKernelGGL(k_hk_parts, dim3((unsigned)std::min(cnt - at0, kHkGridX), (unsigned)hp.cls_parts[c]), dim3(kHkRows), 0, s,
-                                   (const double*)(w.buf + at.pts), (const int64_t*)(w.buf + at.off), (const int32_t*)(w.buf + at.pairs),
-                                   (const int32_t*)(w.buf + at.order) + first + at0, poff, -hp.c8, part);
+                                   call.at<const double>(at.pts), call.at<const int64_t>(at.off), call.at<const int32_t>(at.pairs),
+                                   call.at<const int32_t>(at.order) + first + at0, poff, -hp.c8, part);
                 HIPC(hipGetLastError());
             }
         first += cnt;
@@ -90,25 +78,16 @@ extern "C" int tda_heat_kernel(const tda_hk_args* a, tda_hk_result** out) {
     for (int64_t w0 = 0; w0 < (int64_t)W; w0 += kHkGridX) {
         const int64_t n = std::min((int64_t)W - w0, kHkGridX);
         hipLaunchKernelGGL(k_hk_sum, dim3((unsigned)((n + per_block - 1) / per_block)), dim3(kHkSumThreads), 0, s, (const double*)part, poff, w0,
-                           w0 + n, hp.cn, kern);
+                           w0 + n, hp.cn, call.at<double>(o_kern));
         HIPC(hipGetLastError());
     }
-    HIPC(hipMemcpyAsync(R->kern.data(), kern, W * 8, hipMemcpyDeviceToHost, s));
-    HIPC(hipEventRecord(w.ev[1], s));
-    HIPC(hipStreamSynchronize(s));
-    float ms = 0.0f;
-    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+    if (int rc = call.end(R->kern.data(), o_kern, W * 8)) return rc;
     const double* self = R->kern.data() + P;
     for (size_t p = 0; p < P; ++p) {  // the header's order of operations; the sum of the two selfs is commutative
         const double q = (self[pl.pairs[2 * p]] + self[pl.pairs[2 * p + 1]]) - 2.0 * R->kern[p];
         R->dist[p] = q > 0.0 ? std::sqrt(q) : 0.0;
     }
-    R->pub.kern = R->kern.data();
-    R->pub.self = self;
-    R->pub.dist = R->dist.data();
-    R->pub.device_ms = ms;
-    *out = &R.release()->pub;
-    return 0;
+    return dgm_return(R, out, call.ms);
 }
 
 extern "C" void tda_hk_free(tda_hk_result* r) {

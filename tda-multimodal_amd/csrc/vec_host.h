@@ -1,7 +1,7 @@
 // vec_host.h -- host side of tda_landscape and tda_persistence_image
 // (include/tda_dgm.h), part of rips.hip's translation unit (shares its error
-// state and device checks; the plan is dgm_plan.h's VecPlan, the workspace
-// aux_ws.h's).
+// state and device checks; the plan is dgm_plan.h's VecPlan, the frame of the
+// call dgm_call.h's).
 //
 // One call, the shape of the distance entries: drop the non-finite points on the
 // host and sort the diagrams into size classes, upload everything in one copy,
@@ -22,7 +22,7 @@
 // is nothing a size class would change.
 #pragma once
 #include "../../include/tda_dgm.h"
-#include "dgm_plan.h"
+#include "dgm_call.h"
 #include "vec_kernels.h"
 
 namespace {
@@ -69,49 +69,26 @@ extern "C" int tda_landscape(const tda_pl_args* a, tda_pl_result** out) {
     if (!tda_device_ok(a->device)) return fail(TDA_E_NODEVICE, "no gfx950 device at ordinal " + std::to_string(a->device));
     const size_t S = (size_t)pl.S, G = (size_t)a->G, K = (size_t)a->K;
     std::unique_ptr<VecResultImpl<tda_pl_result>> R(new VecResultImpl<tda_pl_result>(pl.S, (int64_t)(K * G)));
-    if (S == 0) {  // nothing to launch
-        *out = &R.release()->pub;
-        return 0;
-    }
+    if (S == 0) return dgm_return(R, out);  // nothing to launch
 
-    Carve cv;
-    const size_t o_pts = cv.take(pl.pts.size() * 8), o_off = cv.take(pl.off.size() * 8), o_order = cv.take(pl.order.size() * 4);
-    const size_t o_grid = cv.take(G * 8);
-    const size_t up_bytes = cv.o;  // the uploaded part
-    const size_t o_out = cv.take(S * K * G * 8);
-    std::vector<char> up(up_bytes);
-    if (!pl.pts.empty()) std::memcpy(up.data() + o_pts, pl.pts.data(), pl.pts.size() * 8);
-    std::memcpy(up.data() + o_off, pl.off.data(), pl.off.size() * 8);
-    std::memcpy(up.data() + o_order, pl.order.data(), pl.order.size() * 4);
-    std::memcpy(up.data() + o_grid, a->grid, G * 8);
-
-    AuxWs& w = aux_ws(kAuxPl, a->device);
-    std::lock_guard<std::mutex> guard(w.mu);
-    if (int rc = aux_open(w, 2)) return rc;
-    if (int rc = aux_lds_attr(w, (const void*)k_pl_tents<64>, pl_lds_bytes(kVecMaxN))) return rc;
-    if (int rc = aux_reserve(w, cv.o)) return rc;
-    hipStream_t s = w.stream;
-    double* dout = (double*)(w.buf + o_out);
-    HIPC(hipEventRecord(w.ev[0], s));
-    HIPC(hipMemcpyAsync(w.buf, up.data(), up_bytes, hipMemcpyHostToDevice, s));
+    DgmCall call;
+    const size_t o_pts = call.upload(pl.pts), o_off = call.upload(pl.off), o_order = call.upload(pl.order);
+    const size_t o_grid = call.upload(a->grid, G * 8);
+    const size_t o_out = call.device(S * K * G * 8);
+    if (int rc = call.begin(kAuxPl, a->device, (const void*)k_pl_tents<64>, pl_lds_bytes(kVecMaxN))) return rc;
     const unsigned tiles = (unsigned)((G + kPlTile - 1) / kPlTile);
     int64_t first = 0;
     for (int c = 0; c < kVecClasses; ++c) {
         const int64_t cnt = pl.cls_cnt[c];
         if (!cnt) continue;
-        pl_launch(c, dim3((unsigned)cnt, tiles), pl_lds_bytes(pl.cls_n[c]), s, (const double*)(w.buf + o_pts), (const int64_t*)(w.buf + o_off),
-                  (const int32_t*)(w.buf + o_order) + first, (const double*)(w.buf + o_grid), (int)G, (int)K, dout);
+        pl_launch(c, dim3((unsigned)cnt, tiles), pl_lds_bytes(pl.cls_n[c]), call.stream(), call.at<const double>(o_pts),
+                  call.at<const int64_t>(o_off), call.at<const int32_t>(o_order) + first, call.at<const double>(o_grid), (int)G, (int)K,
+                  call.at<double>(o_out));
         HIPC(hipGetLastError());
         first += cnt;
     }
-    HIPC(hipMemcpyAsync(R->values.get(), dout, S * K * G * 8, hipMemcpyDeviceToHost, s));
-    HIPC(hipEventRecord(w.ev[1], s));
-    HIPC(hipStreamSynchronize(s));
-    float ms = 0.0f;
-    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-    R->pub.device_ms = ms;
-    *out = &R.release()->pub;
-    return 0;
+    if (int rc = call.end(R->values.get(), o_out, S * K * G * 8)) return rc;
+    return dgm_return(R, out, call.ms);
 }
 
 extern "C" void tda_pl_free(tda_pl_result* r) { vec_free(r); }
@@ -125,47 +102,21 @@ extern "C" int tda_persistence_image(const tda_pi_args* a, tda_pi_result** out) 
     if (!tda_device_ok(a->device)) return fail(TDA_E_NODEVICE, "no gfx950 device at ordinal " + std::to_string(a->device));
     const size_t S = (size_t)pl.S, W = (size_t)a->W, H = (size_t)a->H;
     std::unique_ptr<VecResultImpl<tda_pi_result>> R(new VecResultImpl<tda_pi_result>(pl.S, (int64_t)(W * H)));
-    if (S == 0) {  // nothing to launch
-        *out = &R.release()->pub;
-        return 0;
-    }
+    if (S == 0) return dgm_return(R, out);  // nothing to launch
 
-    Carve cv;
-    const size_t o_pts = cv.take(pl.pts.size() * 8), o_wgt = cv.take(pl.wgt.size() * 8), o_off = cv.take(pl.off.size() * 8);
-    const size_t o_xe = cv.take((W + 1) * 8), o_ye = cv.take((H + 1) * 8);
-    const size_t up_bytes = cv.o;  // the uploaded part
-    const size_t o_out = cv.take(S * W * H * 8);
-    std::vector<char> up(up_bytes);
-    if (!pl.pts.empty()) {
-        std::memcpy(up.data() + o_pts, pl.pts.data(), pl.pts.size() * 8);
-        std::memcpy(up.data() + o_wgt, pl.wgt.data(), pl.wgt.size() * 8);
-    }
-    std::memcpy(up.data() + o_off, pl.off.data(), pl.off.size() * 8);
-    std::memcpy(up.data() + o_xe, a->x_edges, (W + 1) * 8);
-    std::memcpy(up.data() + o_ye, a->y_edges, (H + 1) * 8);
+    DgmCall call;
+    const size_t o_pts = call.upload(pl.pts), o_wgt = call.upload(pl.wgt), o_off = call.upload(pl.off);
+    const size_t o_xe = call.upload(a->x_edges, (W + 1) * 8), o_ye = call.upload(a->y_edges, (H + 1) * 8);
+    const size_t o_out = call.device(S * W * H * 8);
     const double r = 0.70710678118654752440 / a->sigma;  // 1 / (sigma sqrt(2)): a rounded constant, a rounded division
-
-    AuxWs& w = aux_ws(kAuxPi, a->device);
-    std::lock_guard<std::mutex> guard(w.mu);
-    if (int rc = aux_open(w, 2)) return rc;
-    if (int rc = aux_reserve(w, cv.o)) return rc;
-    hipStream_t s = w.stream;
-    double* dout = (double*)(w.buf + o_out);
-    HIPC(hipEventRecord(w.ev[0], s));
-    HIPC(hipMemcpyAsync(w.buf, up.data(), up_bytes, hipMemcpyHostToDevice, s));
+    if (int rc = call.begin(kAuxPi, a->device)) return rc;
     const unsigned tiles = (unsigned)(((W + kPiTile - 1) / kPiTile) * ((H + kPiTile - 1) / kPiTile));
-    hipLaunchKernelGGL(k_pi_image, dim3((unsigned)S, tiles), dim3(kPiThreads), 0, s, (const double*)(w.buf + o_pts),
-                       (const double*)(w.buf + o_wgt), (const int64_t*)(w.buf + o_off), (const double*)(w.buf + o_xe),
-                       (const double*)(w.buf + o_ye), (int)W, (int)H, r, dout);
+    hipLaunchKernelGGL(k_pi_image, dim3((unsigned)S, tiles), dim3(kPiThreads), 0, call.stream(), call.at<const double>(o_pts),
+                       call.at<const double>(o_wgt), call.at<const int64_t>(o_off), call.at<const double>(o_xe), call.at<const double>(o_ye),
+                       (int)W, (int)H, r, call.at<double>(o_out));
     HIPC(hipGetLastError());
-    HIPC(hipMemcpyAsync(R->values.get(), dout, S * W * H * 8, hipMemcpyDeviceToHost, s));
-    HIPC(hipEventRecord(w.ev[1], s));
-    HIPC(hipStreamSynchronize(s));
-    float ms = 0.0f;
-    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-    R->pub.device_ms = ms;
-    *out = &R.release()->pub;
-    return 0;
+    if (int rc = call.end(R->values.get(), o_out, S * W * H * 8)) return rc;
+    return dgm_return(R, out, call.ms);
 }
 
 extern "C" void tda_pi_free(tda_pi_result* r) { vec_free(r); }

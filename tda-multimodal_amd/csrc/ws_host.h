@@ -1,6 +1,6 @@
 // ws_host.h -- host side of tda_wasserstein (include/tda_dgm.h), part of rips.hip's
-// translation unit (shares its error state and device checks; the plan is
-// dgm_plan.h's, the upload's layout dgm_host.h's).
+// translation unit (shares its error state and device checks; the plan and the
+// classes' limits are dgm_plan.h's, the frame of the call dgm_call.h's).
 //
 // One call, the shape of tda_bottleneck: drop the non-finite points on the host,
 // orient every pair canonically (dgm_orient: the kernel sees the same input for
@@ -24,13 +24,12 @@
 // sets the launch shape.
 #pragma once
 #include "../../include/tda_dgm.h"
+#include "dgm_call.h"
 #include "ws_kernels.h"
 
 namespace {
 
-static_assert(kWsMaxN == TDA_WS_MAX_POINTS, "tda_dgm.h and ws_kernels.h disagree");
-
-constexpr int kWsClassN[kPairClasses] = {64, 256, kWsMaxN};  // nm at most; also the workgroup size
+static_assert(kWsMaxN == TDA_WS_MAX_POINTS && kWsClassN[kPairClasses - 1] == kWsMaxN, "tda_dgm.h, dgm_plan.h and ws_kernels.h disagree");
 static_assert(ws_lds_bytes(kWsMaxN, kWsMaxN) <= 64 * 1024, "k_ws_pairs would need hipFuncAttributeMaxDynamicSharedMemorySize");
 
 struct WsResultImpl {
@@ -40,40 +39,18 @@ struct WsResultImpl {
     std::vector<int32_t> match;
 };
 
-// the plan, the pairs oriented (swapped[p]: pair p was exchanged) and, with the matching, moff [P + 1]:
-// where the mates of each pair's first diagram (as oriented) start in the device's match array
-int ws_plan(const tda_ws_args* a, PairPlan& pl, std::vector<uint8_t>& swapped, std::vector<int64_t>& moff) {
-    if (!a) return fail(TDA_E_INVALID, "args is NULL");
-    if (a->S < 0) return fail(TDA_E_INVALID, "S must be >= 0");
-    if (!a->offsets) return fail(TDA_E_INVALID, "offsets is NULL");
-    if (a->flags & ~TDA_WS_WANT_MATCHING) return fail(TDA_E_INVALID, "flags holds an unknown bit");
-    std::string msg;
-    if (int rc = dgm_check_layout(a->points, a->offsets, a->S, a->pairs, a->P, "wasserstein", msg)) return fail(rc, msg);
-    const int64_t P = a->pairs ? a->P : a->S * (a->S - 1) / 2;
-    if (P > TDA_SW_MAX_WORK) return fail(TDA_E_UNSUPPORTED, "wasserstein: more than 2^27 pairs in one call is not supported (split the pairs)");
-    if (int rc = dgm_gather(a->points, a->offsets, a->S, a->pairs, P, pl, msg)) return fail(rc, msg);
-    if (int rc = dgm_classify(pl, PairSize::kMax, kWsClassN, "wasserstein: a diagram with more than 512 finite points is not supported", msg))
-        return fail(rc, msg);
-    dgm_orient(pl, swapped);
-    if (a->flags & TDA_WS_WANT_MATCHING) {
-        moff.assign((size_t)P + 1, 0);
-        for (int64_t p = 0; p < P; ++p) moff[p + 1] = moff[p] + (pl.off[pl.pairs[2 * p] + 1] - pl.off[pl.pairs[2 * p]]);
-        if (moff[P] > TDA_SW_MAX_WORK)
-            return fail(TDA_E_UNSUPPORTED, "wasserstein: a matching of more than 2^27 entries in one call is not supported (split the pairs)");
-    }
-    return 0;
-}
-
 }  // namespace
 
 extern "C" int tda_wasserstein(const tda_ws_args* a, tda_ws_result** out) {
     if (!out) return fail(TDA_E_INVALID, "out is NULL");
     *out = nullptr;
-    PairPlan pl;
-    std::vector<uint8_t> swapped;
-    std::vector<int64_t> moff;
-    if (int rc = ws_plan(a, pl, swapped, moff)) return rc;
+    WsPlan wp;
+    std::string msg;
+    if (int rc = ws_plan(a, wp, msg)) return fail(rc, msg);
     if (!tda_device_ok(a->device)) return fail(TDA_E_NODEVICE, "no gfx950 device at ordinal " + std::to_string(a->device));
+    const PairPlan& pl = wp.pl;
+    const std::vector<uint8_t>& swapped = wp.swapped;
+    const std::vector<int64_t>& moff = wp.moff;
     const size_t P = (size_t)pl.P;
     const bool want = a->flags & TDA_WS_WANT_MATCHING;
     std::unique_ptr<WsResultImpl> R(new WsResultImpl());
@@ -86,46 +63,29 @@ extern "C" int tda_wasserstein(const tda_ws_args* a, tda_ws_result** out) {
         R->match.assign(1, -1);  // never NULL with the flag
         R->pub.match = R->match.data();
     }
-    if (P == 0) {  // nothing to launch
-        *out = &R.release()->pub;
-        return 0;
-    }
+    if (P == 0) return dgm_return(R, out);  // nothing to launch
 
-    Carve cv;
-    const PlanAt at(pl, cv);
-    const size_t o_moff = want ? cv.take(moff.size() * 8) : 0;
-    const size_t up_bytes = cv.o;  // the uploaded part
-    const size_t o_dist = cv.take(P * 8);
+    DgmCall call;
+    const PairAt at(call, pl);
+    const size_t o_moff = want ? call.upload(moff) : 0;
+    const size_t o_dist = call.device(P * 8);
     const size_t n_match = want ? (size_t)moff[P] : 0;
-    const size_t o_match = want ? cv.take(n_match * 4) : 0;
+    const size_t o_match = want ? call.device(n_match * 4) : 0;
     const size_t down_bytes = want ? o_match + n_match * 4 - o_dist : P * 8;  // the downloaded part: dist, then match
-    std::vector<char> up(up_bytes), down(down_bytes);
-    at.pack(pl, up.data());
-    if (want) std::memcpy(up.data() + o_moff, moff.data(), moff.size() * 8);
-
-    AuxWs& w = aux_ws(kAuxWs, a->device);
-    std::lock_guard<std::mutex> guard(w.mu);
-    if (int rc = aux_open(w, 2)) return rc;
-    if (int rc = aux_reserve(w, cv.o)) return rc;
-    hipStream_t s = w.stream;
-    HIPC(hipEventRecord(w.ev[0], s));
-    HIPC(hipMemcpyAsync(w.buf, up.data(), up_bytes, hipMemcpyHostToDevice, s));
+    std::vector<char> down(down_bytes);
+    if (int rc = call.begin(kAuxWs, a->device)) return rc;
     int64_t first = 0;
     for (int c = 0; c < kPairClasses; ++c) {
         const int64_t cnt = pl.cls_cnt[c];
         if (!cnt) continue;
-        hipLaunchKernelGGL(k_ws_pairs, dim3((unsigned)cnt), dim3(kWsClassN[c]), ws_lds_bytes(pl.cls_n[c], pl.cls_n[c]), s,
-                           (const double*)(w.buf + at.pts), (const int64_t*)(w.buf + at.off), (const int32_t*)(w.buf + at.pairs),
-                           (const int32_t*)(w.buf + at.order) + first, (double*)(w.buf + o_dist),
-                           want ? (const int64_t*)(w.buf + o_moff) : nullptr, want ? (int32_t*)(w.buf + o_match) : nullptr);
+        hipLaunchKernelGGL(k_ws_pairs, dim3((unsigned)cnt), dim3(kWsClassN[c]), ws_lds_bytes(pl.cls_n[c], pl.cls_n[c]), call.stream(),
+                           call.at<const double>(at.pts), call.at<const int64_t>(at.off), call.at<const int32_t>(at.pairs),
+                           call.at<const int32_t>(at.order) + first, call.at<double>(o_dist),
+                           want ? call.at<const int64_t>(o_moff) : nullptr, want ? call.at<int32_t>(o_match) : nullptr);
         HIPC(hipGetLastError());
         first += cnt;
     }
-    HIPC(hipMemcpyAsync(down.data(), w.buf + o_dist, down_bytes, hipMemcpyDeviceToHost, s));
-    HIPC(hipEventRecord(w.ev[1], s));
-    HIPC(hipStreamSynchronize(s));
-    float ms = 0.0f;
-    HIPC(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+    if (int rc = call.end(down.data(), o_dist, down_bytes)) return rc;
     std::memcpy(R->dist.data(), down.data(), P * 8);
     // no sum of costs is a NaN (the coordinates are finite), so a NaN is the kernel's word for "a loop bound was hit"
     for (size_t p = 0; p < P; ++p)
@@ -156,9 +116,7 @@ extern "C" int tda_wasserstein(const tda_ws_args* a, tda_ws_result** out) {
         }
         R->pub.match = R->match.data();
     }
-    R->pub.device_ms = ms;
-    *out = &R.release()->pub;
-    return 0;
+    return dgm_return(R, out, call.ms);
 }
 
 extern "C" void tda_ws_free(tda_ws_result* r) {

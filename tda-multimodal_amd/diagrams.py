@@ -108,27 +108,89 @@ def _finite_counts(points, offsets):
     return c[offsets[1:]] - c[offsets[:-1]], int(len(fin) - c[-1])
 
 
-def _call(points, offsets, pairs, M: int, device: int):
-    """One tda_sliced_wasserstein call: (dist (P,), device_ms)."""
-    S = len(offsets) - 1
-    if (S < 2) if pairs is None else not len(pairs):  # no pair: nothing to launch
-        return np.zeros(0), 0.0
-    a = _lib.SwArgs()
+# What a call is measured by against its entry's limit, from the finite counts of its S (+ S2) diagrams.
+def _top_diagram(cnt, S, S2, block):
+    """The largest diagram of the call (the heat kernel, the vectorisations)."""
+    return cnt.max() if len(cnt) else 0
+
+
+def _top_paired_diagram(cnt, S, S2, block):
+    """The largest diagram of a call that holds a pair (bottleneck, Wasserstein)."""
+    return cnt.max() if (S and S2 if block else S >= 2) else 0
+
+
+def _top_pair(cnt, S, S2, block):
+    """The two largest diagrams together or, with ``other``, the largest of each side (sliced Wasserstein)."""
+    if block:
+        return (cnt[:S].max() + cnt[S:].max()) if S and S2 else 0
+    return np.sort(cnt)[-2:].sum() if S >= 2 else 0
+
+
+def _inputs(dgms, other, dim: int, limit: int, top=_top_diagram, holds="a diagram holds {} finite points"):
+    """(points, offsets, pairs or None, S, S') of a call on ``dgms`` or, with ``other``, on both lists
+    and the pairs of the (S, S') block; the entry's limit checked (``top``: what is measured against
+    it, ``holds``: how the refusal names it) and the non-finite points reported, before any library call."""
+    pts, off = _flatten(dgms, dim)
+    S = S2 = len(off) - 1
+    pairs = None
+    if other is not None:
+        pts2, off2 = _flatten(other, dim)
+        S2 = len(off2) - 1
+        pts, off = np.concatenate([pts, pts2]), np.concatenate([off, off[-1] + off2[1:]])
+        pairs = np.stack(np.meshgrid(np.arange(S), S + np.arange(S2), indexing="ij"), -1).reshape(-1, 2).astype(np.int32)
+    cnt, dropped = _finite_counts(pts, off)
+    n = top(cnt, S, S2, other is not None)
+    if n > limit:
+        raise NotImplementedError(f"{holds.format(int(n))}: more than {limit} is not supported")
+    if dropped:
+        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
+    return pts, off, pairs, S, S2
+
+
+def _matrix(values, S: int, S2: int, block: bool):
+    """The (S, S') block of a call with ``other``, or the symmetric (S, S) matrix with a zero diagonal."""
+    if block:
+        return values.reshape(S, S2)
+    D = np.zeros((S, S))
+    D[np.triu_indices(S, 1)] = values  # row-major i < j: the order of the library's all-pairs result
+    return D + D.T
+
+
+def _library_call(entry: str, points, offsets, pairs, read, **fields):
+    """One call of an entry of tda_dgm.h (_lib.DGM_ENTRIES): the common fields and ``fields`` set, the
+    return code checked; returns ``read(result struct)`` (owned arrays: _owned) and frees the result."""
+    symbol, free, Args, Result = _lib.DGM_ENTRIES[entry]
+    a = Args()
     a.points = points.ctypes.data if len(points) else None
     a.offsets = offsets.ctypes.data
-    a.S = S
+    a.S = len(offsets) - 1
     if pairs is not None:
         a.pairs, a.P = pairs.ctypes.data, len(pairs)
-    a.M, a.device = M, int(device)
+    for name, value in fields.items():
+        setattr(a, name, value)
     L = _lib.lib()
-    res = ctypes.POINTER(_lib.SwResult)()
-    _lib.check(L.tda_sliced_wasserstein(ctypes.byref(a), ctypes.byref(res)))
+    res = ctypes.POINTER(Result)()
+    _lib.check(getattr(L, symbol)(ctypes.byref(a), ctypes.byref(res)))
     try:
-        r = res.contents
-        out = np.frombuffer(ctypes.string_at(r.dist, r.P * 8), dtype=np.float64).copy() if r.P else np.zeros(0)
-        return out, float(r.device_ms)
+        return read(res.contents)
     finally:
-        L.tda_sw_free(res)
+        getattr(L, free)(res)
+
+
+def _owned(p, n: int, dtype=np.float64):
+    """n values at the result's pointer p, copied: they outlive the result."""
+    return np.frombuffer(ctypes.string_at(p, n * np.dtype(dtype).itemsize), dtype=dtype).copy() if n else np.zeros(0, dtype)
+
+
+def _no_pair(offsets, pairs) -> bool:
+    return len(offsets) < 3 if pairs is None else not len(pairs)
+
+
+def _call_dist(entry: str, points, offsets, pairs, **fields):
+    """One tda_sliced_wasserstein or tda_bottleneck call: (dist (P,), device_ms)."""
+    if _no_pair(offsets, pairs):  # nothing to launch
+        return np.zeros(0), 0.0
+    return _library_call(entry, points, offsets, pairs, lambda r: (_owned(r.dist, r.P), float(r.device_ms)), **fields)
 
 
 def sliced_wasserstein_matrix(dgms, M: int = 50, other=None, device: int = 0, dim: int = 1, return_time: bool = False):
@@ -142,32 +204,9 @@ def sliced_wasserstein_matrix(dgms, M: int = 50, other=None, device: int = 0, di
     ``dgms`` against ``other``; with ``return_time`` also the call's device
     time in ms.  A pair's value is the same bits in any call that holds it."""
     M = _check_M(M)
-    pts, off = _flatten(dgms, dim)
-    S = len(off) - 1
-    if other is None:
-        pairs = None
-        cnt, dropped = _finite_counts(pts, off)
-        top = np.sort(cnt)[-2:].sum() if S >= 2 else 0
-    else:
-        pts2, off2 = _flatten(other, dim)
-        S2 = len(off2) - 1
-        pts, off = np.concatenate([pts, pts2]), np.concatenate([off, off[-1] + off2[1:]])
-        pairs = np.stack(np.meshgrid(np.arange(S), S + np.arange(S2), indexing="ij"), -1).reshape(-1, 2).astype(np.int32)
-        cnt, dropped = _finite_counts(pts, off)
-        top = (cnt[:S].max() + cnt[S:].max()) if S and S2 else 0
-    if top > _lib.TDA_SW_MAX_POINTS:
-        raise NotImplementedError(f"a pair of diagrams holds {int(top)} finite points together: more than "
-                                  f"{_lib.TDA_SW_MAX_POINTS} is not supported")
-    if dropped:
-        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
-    dist, ms = _call(pts, off, pairs, M, device)
-    if other is None:
-        D = np.zeros((S, S))
-        iu = np.triu_indices(S, 1)  # row-major i < j: the order of the library's all-pairs result
-        D[iu] = dist
-        D = D + D.T
-    else:
-        D = dist.reshape(S, S2)
+    pts, off, pairs, S, S2 = _inputs(dgms, other, dim, _lib.TDA_SW_MAX_POINTS, _top_pair, "a pair of diagrams holds {} finite points together")
+    dist, ms = _call_dist("sw", pts, off, pairs, M=M, device=int(device))
+    D = _matrix(dist, S, S2, other is not None)
     return (D, ms) if return_time else D
 
 
@@ -181,29 +220,6 @@ def sliced_wasserstein(PD1, PD2, M: int = 50, device: int = 0) -> float:
     return float(sliced_wasserstein_matrix([PD1], M=M, other=[PD2], device=device)[0, 0])
 
 
-def _call_bn(points, offsets, pairs, device: int):
-    """One tda_bottleneck call: (dist (P,), device_ms)."""
-    S = len(offsets) - 1
-    if (S < 2) if pairs is None else not len(pairs):  # no pair: nothing to launch
-        return np.zeros(0), 0.0
-    a = _lib.BnArgs()
-    a.points = points.ctypes.data if len(points) else None
-    a.offsets = offsets.ctypes.data
-    a.S = S
-    if pairs is not None:
-        a.pairs, a.P = pairs.ctypes.data, len(pairs)
-    a.device = int(device)
-    L = _lib.lib()
-    res = ctypes.POINTER(_lib.BnResult)()
-    _lib.check(L.tda_bottleneck(ctypes.byref(a), ctypes.byref(res)))
-    try:
-        r = res.contents
-        out = np.frombuffer(ctypes.string_at(r.dist, r.P * 8), dtype=np.float64).copy() if r.P else np.zeros(0)
-        return out, float(r.device_ms)
-    finally:
-        L.tda_bn_free(res)
-
-
 def bottleneck_matrix(dgms, other=None, device: int = 0, dim: int = 1, return_time: bool = False):
     """Bottleneck distances between every pair of diagrams, one library call.
 
@@ -212,31 +228,9 @@ def bottleneck_matrix(dgms, other=None, device: int = 0, dim: int = 1, return_ti
     :class:`LayerResult`; the (S, S) matrix is symmetric with a zero diagonal,
     the (S, S') matrix is ``dgms`` against ``other``.  Every value is exact, and
     the same bits in any call that holds the pair, in either orientation."""
-    pts, off = _flatten(dgms, dim)
-    S = len(off) - 1
-    if other is None:
-        pairs = None
-        cnt, dropped = _finite_counts(pts, off)
-        top = cnt.max() if S >= 2 else 0
-    else:
-        pts2, off2 = _flatten(other, dim)
-        S2 = len(off2) - 1
-        pts, off = np.concatenate([pts, pts2]), np.concatenate([off, off[-1] + off2[1:]])
-        pairs = np.stack(np.meshgrid(np.arange(S), S + np.arange(S2), indexing="ij"), -1).reshape(-1, 2).astype(np.int32)
-        cnt, dropped = _finite_counts(pts, off)
-        top = cnt.max() if S and S2 else 0
-    if top > _lib.TDA_BN_MAX_POINTS:
-        raise NotImplementedError(f"a diagram holds {int(top)} finite points: more than {_lib.TDA_BN_MAX_POINTS} is not supported")
-    if dropped:
-        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
-    dist, ms = _call_bn(pts, off, pairs, device)
-    if other is None:
-        D = np.zeros((S, S))
-        iu = np.triu_indices(S, 1)  # row-major i < j: the order of the library's all-pairs result
-        D[iu] = dist
-        D = D + D.T
-    else:
-        D = dist.reshape(S, S2)
+    pts, off, pairs, S, S2 = _inputs(dgms, other, dim, _lib.TDA_BN_MAX_POINTS, _top_paired_diagram)
+    dist, ms = _call_dist("bn", pts, off, pairs, device=int(device))
+    D = _matrix(dist, S, S2, other is not None)
     return (D, ms) if return_time else D
 
 
@@ -258,52 +252,23 @@ _SQRT1_2 = 0.70710678118654752440  # the factor of a point's L2 distance to the 
 
 def _call_ws(points, offsets, pairs, device: int, want_matching: bool = False):
     """One tda_wasserstein call: (dist (P,), device_ms, match_off (P + 1,) or None, match or None)."""
-    S = len(offsets) - 1
-    if (S < 2) if pairs is None else not len(pairs):  # no pair: nothing to launch
+    if _no_pair(offsets, pairs):  # nothing to launch
         return np.zeros(0), 0.0, None, None
-    a = _lib.WsArgs()
-    a.points = points.ctypes.data if len(points) else None
-    a.offsets = offsets.ctypes.data
-    a.S = S
-    if pairs is not None:
-        a.pairs, a.P = pairs.ctypes.data, len(pairs)
-    a.device, a.flags = int(device), _lib.TDA_WS_WANT_MATCHING if want_matching else 0
-    L = _lib.lib()
-    res = ctypes.POINTER(_lib.WsResult)()
-    _lib.check(L.tda_wasserstein(ctypes.byref(a), ctypes.byref(res)))
-    try:
-        r = res.contents
-        out = np.frombuffer(ctypes.string_at(r.dist, r.P * 8), dtype=np.float64).copy() if r.P else np.zeros(0)
+    flags = _lib.TDA_WS_WANT_MATCHING if want_matching else 0
+
+    def read(r):
         moff = match = None
         if want_matching:
-            moff = np.frombuffer(ctypes.string_at(r.match_off, (r.P + 1) * 8), dtype=np.int64).copy()
-            match = np.frombuffer(ctypes.string_at(r.match, int(moff[-1]) * 4), dtype=np.int32).copy()
-        return out, float(r.device_ms), moff, match
-    finally:
-        L.tda_ws_free(res)
+            moff = _owned(r.match_off, r.P + 1, np.int64)
+            match = _owned(r.match, int(moff[-1]), np.int32)
+        return _owned(r.dist, r.P), float(r.device_ms), moff, match
+
+    return _library_call("ws", points, offsets, pairs, read, device=int(device), flags=flags)
 
 
 def _ws_inputs(dgms, other, dim: int):
-    """(points, offsets, pairs or None, S, S') of a Wasserstein call, the limit checked and the
-    non-finite points reported."""
-    pts, off = _flatten(dgms, dim)
-    S = S2 = len(off) - 1
-    if other is None:
-        pairs = None
-        cnt, dropped = _finite_counts(pts, off)
-        top = cnt.max() if S >= 2 else 0
-    else:
-        pts2, off2 = _flatten(other, dim)
-        S2 = len(off2) - 1
-        pts, off = np.concatenate([pts, pts2]), np.concatenate([off, off[-1] + off2[1:]])
-        pairs = np.stack(np.meshgrid(np.arange(S), S + np.arange(S2), indexing="ij"), -1).reshape(-1, 2).astype(np.int32)
-        cnt, dropped = _finite_counts(pts, off)
-        top = cnt.max() if S and S2 else 0
-    if top > _lib.TDA_WS_MAX_POINTS:
-        raise NotImplementedError(f"a diagram holds {int(top)} finite points: more than {_lib.TDA_WS_MAX_POINTS} is not supported")
-    if dropped:
-        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
-    return pts, off, pairs, S, S2
+    """:func:`_inputs` of a Wasserstein call."""
+    return _inputs(dgms, other, dim, _lib.TDA_WS_MAX_POINTS, _top_paired_diagram)
 
 
 def wasserstein_matrix(dgms, other=None, device: int = 0, dim: int = 1, return_time: bool = False):
@@ -316,13 +281,7 @@ def wasserstein_matrix(dgms, other=None, device: int = 0, dim: int = 1, return_t
     the pair, in either orientation."""
     pts, off, pairs, S, S2 = _ws_inputs(dgms, other, dim)
     dist, ms, _, _ = _call_ws(pts, off, pairs, device)
-    if other is None:
-        D = np.zeros((S, S))
-        iu = np.triu_indices(S, 1)  # row-major i < j: the order of the library's all-pairs result
-        D[iu] = dist
-        D = D + D.T
-    else:
-        D = dist.reshape(S, S2)
+    D = _matrix(dist, S, S2, other is not None)
     return (D, ms) if return_time else D
 
 
@@ -377,61 +336,26 @@ def _check_sigma(sigma) -> float:
 def _call_hk(points, offsets, pairs, sigma: float, device: int):
     """One tda_heat_kernel call: (kern (P,), self (S,), dist (P,), device_ms)."""
     S = len(offsets) - 1
-    a = _lib.HkArgs()
-    a.points = points.ctypes.data if len(points) else None
-    a.offsets = offsets.ctypes.data
-    a.S = S
-    if pairs is not None:
-        a.pairs, a.P = pairs.ctypes.data, len(pairs)
-    a.sigma, a.device = sigma, int(device)
-    L = _lib.lib()
-    res = ctypes.POINTER(_lib.HkResult)()
-    _lib.check(L.tda_heat_kernel(ctypes.byref(a), ctypes.byref(res)))
-    try:
-        r = res.contents
-        get = lambda p, n: np.frombuffer(ctypes.string_at(p, n * 8), dtype=np.float64).copy() if n else np.zeros(0)  # noqa: E731
-        return get(r.kern, r.P), get(r.self, S), get(r.dist, r.P), float(r.device_ms)
-    finally:
-        L.tda_hk_free(res)
+    read = lambda r: (_owned(r.kern, r.P), _owned(r.self, S), _owned(r.dist, r.P), float(r.device_ms))  # noqa: E731
+    return _library_call("hk", points, offsets, pairs, read, sigma=sigma, device=int(device))
 
 
 def _hk_inputs(dgms, other, dim: int):
-    """(points, offsets, pairs or None, S, S') of a heat kernel call, the limit checked and the
-    non-finite points reported."""
-    pts, off = _flatten(dgms, dim)
-    S = S2 = len(off) - 1
-    pairs = None
-    if other is not None:
-        pts2, off2 = _flatten(other, dim)
-        S2 = len(off2) - 1
-        pts, off = np.concatenate([pts, pts2]), np.concatenate([off, off[-1] + off2[1:]])
-        pairs = np.stack(np.meshgrid(np.arange(S), S + np.arange(S2), indexing="ij"), -1).reshape(-1, 2).astype(np.int32)
-    cnt, dropped = _finite_counts(pts, off)
-    if len(cnt) and cnt.max() > _lib.TDA_HK_MAX_POINTS:
-        raise NotImplementedError(f"a diagram holds {int(cnt.max())} finite points: more than {_lib.TDA_HK_MAX_POINTS} is not supported")
-    if dropped:
-        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
-    return pts, off, pairs, S, S2
+    """:func:`_inputs` of a heat kernel call."""
+    return _inputs(dgms, other, dim, _lib.TDA_HK_MAX_POINTS)
 
 
 def _hk_matrix(dgms, sigma, other, device: int, dim: int, want_kernel: bool):
     sigma = _check_sigma(sigma)
     pts, off, pairs, S, S2 = _hk_inputs(dgms, other, dim)
-    if other is None:
-        # the distances of fewer than two diagrams and the Gram matrix of none: nothing to launch
-        if S == 0 or (S == 1 and not want_kernel):
-            return np.zeros((S, S)), 0.0
-        kern, self_, dist, ms = _call_hk(pts, off, None, sigma, device)
-        D = np.zeros((S, S))
-        D[np.triu_indices(S, 1)] = kern if want_kernel else dist  # row-major i < j: the order of the library's all-pairs result
-        D = D + D.T
-        if want_kernel:
-            D[np.diag_indices(S)] = self_
-        return D, ms
-    if S == 0 or S2 == 0:
+    # the distances of fewer than two diagrams and the Gram matrix of none: nothing to launch
+    if S == 0 or S2 == 0 or (other is None and S == 1 and not want_kernel):
         return np.zeros((S, S2)), 0.0
-    kern, _, dist, ms = _call_hk(pts, off, pairs, sigma, device)
-    return (kern if want_kernel else dist).reshape(S, S2), ms
+    kern, self_, dist, ms = _call_hk(pts, off, pairs, sigma, device)
+    D = _matrix(kern if want_kernel else dist, S, S2, other is not None)
+    if want_kernel and other is None:
+        D[np.diag_indices(S)] = self_
+    return D, ms
 
 
 def heat_matrix(dgms, sigma: float = 0.4, other=None, device: int = 0, dim: int = 1, return_time: bool = False):
@@ -473,15 +397,8 @@ def heat(dgm1, dgm2, sigma: float = 0.4, device: int = 0) -> float:
 
 # ---------------------------------------------------------------- vectorisations (tda_landscape, tda_persistence_image)
 def _vec_inputs(dgms, dim: int):
-    """(points, offsets, S) of a landscape or image call, the limit checked and the non-finite
-    points reported."""
-    pts, off = _flatten(dgms, dim)
-    S = len(off) - 1
-    cnt, dropped = _finite_counts(pts, off)
-    if S and cnt.max() > _lib.TDA_VEC_MAX_POINTS:
-        raise NotImplementedError(f"a diagram holds {int(cnt.max())} finite points: more than {_lib.TDA_VEC_MAX_POINTS} is not supported")
-    if dropped:
-        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
+    """(points, offsets, S): :func:`_inputs` of a landscape or image call."""
+    pts, off, _, S, _ = _inputs(dgms, None, dim, _lib.TDA_VEC_MAX_POINTS)
     return pts, off, S
 
 
@@ -502,20 +419,8 @@ def _check_out(S: int, F: int):
 
 def _call_pl(points, offsets, grid, K: int, device: int):
     """One tda_landscape call: (values (S, K, G), device_ms)."""
-    a = _lib.PlArgs()
-    a.points = points.ctypes.data if len(points) else None
-    a.offsets = offsets.ctypes.data
-    a.S = len(offsets) - 1
-    a.grid, a.G, a.K, a.device = grid.ctypes.data, len(grid), K, int(device)
-    L = _lib.lib()
-    res = ctypes.POINTER(_lib.PlResult)()
-    _lib.check(L.tda_landscape(ctypes.byref(a), ctypes.byref(res)))
-    try:
-        r = res.contents
-        out = np.frombuffer(ctypes.string_at(r.values, r.S * r.F * 8), dtype=np.float64).copy()
-        return out.reshape(r.S, K, len(grid)), float(r.device_ms)
-    finally:
-        L.tda_pl_free(res)
+    read = lambda r: (_owned(r.values, r.S * r.F).reshape(r.S, K, len(grid)), float(r.device_ms))  # noqa: E731
+    return _library_call("pl", points, offsets, None, read, grid=grid.ctypes.data, G=len(grid), K=K, device=int(device))
 
 
 def persistence_landscapes(dgms, start=None, stop=None, num_steps: int = 500, depth: int = 10, dim: int = 1, device: int = 0,
@@ -565,21 +470,10 @@ def persistence_landscape(dgm, start=None, stop=None, num_steps: int = 500, dept
 
 def _call_pi(points, offsets, xe, ye, sigma: float, power: float, device: int):
     """One tda_persistence_image call: (values (S, W, H), device_ms)."""
-    a = _lib.PiArgs()
-    a.points = points.ctypes.data if len(points) else None
-    a.offsets = offsets.ctypes.data
-    a.S = len(offsets) - 1
-    a.x_edges, a.y_edges, a.W, a.H = xe.ctypes.data, ye.ctypes.data, len(xe) - 1, len(ye) - 1
-    a.sigma, a.weight_power, a.device = sigma, power, int(device)
-    L = _lib.lib()
-    res = ctypes.POINTER(_lib.PiResult)()
-    _lib.check(L.tda_persistence_image(ctypes.byref(a), ctypes.byref(res)))
-    try:
-        r = res.contents
-        out = np.frombuffer(ctypes.string_at(r.values, r.S * r.F * 8), dtype=np.float64).copy()
-        return out.reshape(r.S, len(xe) - 1, len(ye) - 1), float(r.device_ms)
-    finally:
-        L.tda_pi_free(res)
+    W, H = len(xe) - 1, len(ye) - 1
+    read = lambda r: (_owned(r.values, r.S * r.F).reshape(r.S, W, H), float(r.device_ms))  # noqa: E731
+    return _library_call("pi", points, offsets, None, read, x_edges=xe.ctypes.data, y_edges=ye.ctypes.data, W=W, H=H, sigma=sigma,
+                         weight_power=power, device=int(device))
 
 
 def _edges(name: str, rng, n: int):

@@ -5,6 +5,10 @@
 // P = -1.  Coordinates are read with strtod, so nan, inf and -inf are values.  The calls are those
 // of sw_plan / bn_plan: dgm_check_layout, dgm_gather, dgm_classify.  Per case either
 // "err <code> <message>" or "ok" and six lines: pts, off, pairs, order, cls_cnt, cls_n.
+// A case that starts with sw, bn or ws instead calls that entry's whole plan on an args struct:
+//     entry  args(0 = NULL, 1)  S  noff  offsets[noff]  rows  points[2 * rows]  P  pairs[2 * P]  extra
+// noff = -1: offsets == NULL (S is given apart, so that it can be negative); extra is M (sw),
+// reserved (bn) or flags (ws).  The output is the same; the pairs of ws are as oriented.
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -20,10 +24,20 @@ static void line(const char* name, const T* v, size_t n) {
 
 int main() {
     using namespace tda;
-    int measure, limits[kPairClasses];
-    long long S, rows, P;
-    while (std::cin >> measure >> limits[0] >> limits[1] >> limits[2] >> S) {
-        std::vector<int64_t> off((size_t)S + 1);
+    int measure = 0, limits[kPairClasses] = {}, have_args = 1, extra = 0;
+    long long S, rows, P, noff;
+    std::string head;
+    while (std::cin >> head) {
+        const bool whole = head == "sw" || head == "bn" || head == "ws";
+        if (whole) {
+            std::cin >> have_args >> S >> noff;
+        } else {
+            measure = atoi(head.c_str());
+            std::cin >> limits[0] >> limits[1] >> limits[2] >> S;
+            noff = S + 1;
+        }
+        if (!std::cin) return 2;
+        std::vector<int64_t> off(noff > 0 ? (size_t)noff : 0);
         for (auto& o : off) std::cin >> o;
         std::cin >> rows;
         std::vector<double> pts(rows > 0 ? (size_t)rows * 2 : 0);
@@ -35,16 +49,38 @@ int main() {
         std::cin >> P;
         std::vector<int32_t> prs(P > 0 ? (size_t)P * 2 : 0);
         for (auto& q : prs) std::cin >> q;
+        if (whole) std::cin >> extra;
         if (!std::cin) return 2;
         static const int32_t none = 0;  // something to point at for a list that is empty or refused
         const int32_t* pairs = P == -1 ? nullptr : prs.empty() ? &none : prs.data();
         const int64_t Parg = P == -2 ? -1 : P;
 
         PairPlan pl;
+        WsPlan wp;
         std::string msg;
-        int rc = dgm_check_layout(rows < 0 ? nullptr : pts.data(), off.data(), S, pairs, Parg, "test", msg);
-        if (!rc) rc = dgm_gather(pts.data(), off.data(), S, pairs, pairs ? Parg : S * (S - 1) / 2, pl, msg);
-        if (!rc) rc = dgm_classify(pl, measure ? PairSize::kMax : PairSize::kSum, limits, "too large", msg);
+        int rc;
+        if (whole) {
+            const double* points = rows < 0 ? nullptr : pts.data();
+            const int64_t* offsets = noff < 0 ? nullptr : off.data();
+            if (head == "sw") {
+                tda_sw_args a = {};
+                a.points = points, a.offsets = offsets, a.S = S, a.pairs = pairs, a.P = Parg, a.M = extra;
+                rc = sw_plan(have_args ? &a : nullptr, pl, msg);
+            } else if (head == "bn") {
+                tda_bn_args a = {};
+                a.points = points, a.offsets = offsets, a.S = S, a.pairs = pairs, a.P = Parg, a.reserved = extra;
+                rc = bn_plan(have_args ? &a : nullptr, pl, msg);
+            } else {
+                tda_ws_args a = {};
+                a.points = points, a.offsets = offsets, a.S = S, a.pairs = pairs, a.P = Parg, a.flags = extra;
+                rc = ws_plan(have_args ? &a : nullptr, wp, msg);
+                pl = wp.pl;
+            }
+        } else {
+            rc = dgm_check_layout(rows < 0 ? nullptr : pts.data(), off.data(), S, pairs, Parg, "test", msg);
+            if (!rc) rc = dgm_gather(pts.data(), off.data(), S, pairs, pairs ? Parg : S * (S - 1) / 2, pl, msg);
+            if (!rc) rc = dgm_classify(pl, measure ? PairSize::kMax : PairSize::kSum, limits, "too large", msg);
+        }
         if (rc) {
             printf("err %d %s\n", rc, msg.c_str());
             continue;

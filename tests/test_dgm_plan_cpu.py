@@ -1,9 +1,10 @@
-"""The host plan of the two diagram distances (csrc/dgm_plan.h: dgm_check_layout, dgm_gather,
-dgm_classify) against a numpy restatement (CPU).
+"""The host plan of the diagram distances (csrc/dgm_plan.h: dgm_check_layout, dgm_gather,
+dgm_classify) against a numpy restatement, and the whole plans sw_plan, bn_plan and ws_plan on
+argument structs (CPU).
 
 tests/dgm_plan_main.cpp includes only dgm_plan.h; it is compiled with g++ under the address and
 undefined-behaviour sanitizers and run once per test as a program of its own.  The class limits are
-those of dgm_host.h (a pair's n1 + n2: 128 / 1024 / 4096) and bn_host.h (max(n1, n2): 64 / 256 / 512).
+those of sliced Wasserstein (a pair's n1 + n2: 128 / 1024 / 4096) and bottleneck (max(n1, n2): 64 / 256 / 512).
 """
 import os
 import subprocess
@@ -178,3 +179,79 @@ def test_layout_errors_and_their_messages(plan_exe):
     assert run(plan_exe, cases) == [("err", INVALID, m) for m in msgs]
     # no rows at all: points may be NULL
     assert run(plan_exe, [(SUM, [0, 0, 0], None, None)])[0] == expected(SUM, [0, 0, 0], None, None)
+
+
+# ---------------------------------------------------------------- the whole plans (sw_plan, bn_plan, ws_plan)
+# The expected codes and messages are those tda_sliced_wasserstein, tda_bottleneck and tda_wasserstein
+# have always given for these arguments (the checks run before any device work), in their order.
+EXTRA = {"sw": 50, "bn": 0, "ws": 0}  # M / reserved / flags of a good call
+OVER = {"sw": (4097, "sliced Wasserstein: a pair of diagrams with more than 4096 finite points together is not supported"),
+        "bn": (513, "bottleneck: a diagram with more than 512 finite points is not supported"),
+        "ws": (513, "wasserstein: a diagram with more than 512 finite points is not supported")}
+BAD_EXTRA = {"sw": [(0, INVALID, "M must be >= 1"), (1025, UNSUPPORTED, "sliced Wasserstein: M > 1024 directions is not supported")],
+             "bn": [(1, INVALID, "reserved must be 0")],
+             "ws": [(2, INVALID, "flags holds an unknown bit")]}
+
+
+def run_whole(exe, cases):
+    """cases: dicts of entry, off, pts and optionally args (False: NULL), S, pairs, extra -> as run()"""
+    text = []
+    for c in cases:
+        off, pts, pairs = c["off"], c["pts"], c.get("pairs")
+        t = [c["entry"], int(c.get("args", True)), c.get("S", 0 if off is None else len(off) - 1)]
+        t += [-1] if off is None else [len(off), *off]
+        t += [-1] if pts is None else [len(pts), *(repr(float(x)) for x in np.asarray(pts, np.float64).ravel())]
+        t += [-1] if pairs is None else [len(pairs), *np.asarray(pairs).ravel()]
+        t += [c.get("extra", EXTRA[c["entry"]])]
+        text.append(" ".join(map(str, t)))
+    r = subprocess.run([exe], input="\n".join(text) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines, out = r.stdout.split("\n"), []
+    while lines and lines[0]:
+        head = lines.pop(0).split(" ", 2)
+        if head[0] == "err":
+            out.append(("err", int(head[1]), head[2]))
+            continue
+        assert head == ["ok"]
+        out.append(("ok", {f[0]: [float(x) if f[0] == "pts" else int(x) for x in f[1:]] for f in (lines.pop(0).split() for _ in range(6))}))
+    assert len(out) == len(cases)
+    return out
+
+
+@pytest.mark.parametrize("entry", ("sw", "bn", "ws"))
+def test_whole_plan_accepts_a_tiny_call(plan_exe, entry):
+    """S = 3 diagrams of 0, 1 and 2 points, every pair: one class; tda_wasserstein puts the longer diagram first."""
+    off, pts = diagrams([0, 1, 2], seed=11)
+    (tag, got), = run_whole(plan_exe, [dict(entry=entry, off=off, pts=pts)])
+    assert tag == "ok"
+    assert got == {
+        "pts": pts.ravel().tolist(),
+        "off": [0, 0, 1, 3],
+        "pairs": [1, 0, 2, 0, 2, 1] if entry == "ws" else [0, 1, 0, 2, 1, 2],
+        "order": [0, 1, 2],
+        "cls_cnt": [3, 0, 0],
+        "cls_n": [3 if entry == "sw" else 2, 0, 0],
+    }
+
+
+@pytest.mark.parametrize("entry", ("sw", "bn", "ws"))
+def test_whole_plan_refusals(plan_exe, entry):
+    off, pts = diagrams([0, 1, 2], seed=11)
+    n_over, too_large = OVER[entry]
+    off_over, pts_over = diagrams([n_over, 0], seed=12)
+    good = dict(entry=entry, off=off, pts=pts)
+    cases = [
+        (dict(good, args=False), INVALID, "args is NULL"),
+        (dict(good, S=-1), INVALID, "S must be >= 0"),
+        (dict(good, off=None, S=3), INVALID, "offsets is NULL"),
+        *((dict(good, extra=x), code, m) for x, code, m in BAD_EXTRA[entry]),
+        (dict(good, off=[1, 1, 2, 4]), INVALID, "offsets[0] must be 0"),
+        (dict(good, pairs=[(0, 1), (2, 3)]), INVALID, "pairs holds an index outside [0, S)"),
+        (dict(entry=entry, off=off_over, pts=pts_over), UNSUPPORTED, too_large),
+        # the entry's own check comes before the layout's
+        (dict(good, off=[1, 1, 2, 4], extra=BAD_EXTRA[entry][0][0]), *BAD_EXTRA[entry][0][1:]),
+    ]
+    assert run_whole(plan_exe, [c for c, _, _ in cases]) == [("err", code, m) for _, code, m in cases]
+    # one point fewer is accepted
+    off_at, pts_at = diagrams([n_over - 1, 0], seed=12)
+    assert run_whole(plan_exe, [dict(entry=entry, off=off_at, pts=pts_at)])[0][0] == "ok"
