@@ -286,6 +286,63 @@ int tda_greedy_perm(const tda_greedy_args *args, tda_greedy_result **out);
 void tda_greedy_free(tda_greedy_result *r);
 
 /*
+ * Resamples of L layers on the GPU: the device stage of the bootstrap
+ * confidence bands of persistence diagrams (Fasy et al. 2014, Chazal et al.
+ * 2014).  A resample b of a layer is the m points idx[b][0 .. m-1] of its N
+ * (with or without repetition; the table is the caller's).  Per layer, on the
+ * library's own f32 distance matrix dm (as tda_greedy_perm: the sklearn-exact
+ * kernels for f32 points; for distance-matrix input the upper triangle,
+ * diagonal 0), the call returns
+ *     hausdorff[l][b] = max_i min_{j < m} dm[l][idx[b][j]][i]
+ * the Hausdorff distance between the cloud and the resample (a resample is a
+ * subset of the cloud, so the other directed distance is 0).  Every output is
+ * a value of dm, copied and compared, never computed: results are exact and
+ * independent of any reduction order.  The comparisons are `<` and `>`: a NaN
+ * in dm (possible only in device input, which is not checked; host input is
+ * refused by the Python binding) is skipped, where numpy's min / max would
+ * propagate it.
+ * Why the Hausdorff distance: for the Rips filtration parameterised by the
+ * diameter (as here), d_B(dgm(X), dgm(X*)) <= 2 d_GH(X, X*) <= 2 H(X, X*)
+ * (Chazal, de Silva and Oudot 2014), so 2 H bounds, per resample, how far any
+ * diagram moves, at the cost of no persistence computation.
+ * The call runs on a stream of its own (not a slot's) and synchronises before
+ * it returns.  Its device workspace holds the distance stage of Lc layers at a
+ * time, Lc the largest count that stays within TDA_GREEDY_WS_BYTES (at least
+ * one layer; a table per layer counts in), and beside that, whole, the (L, B)
+ * result (L * B * 4 bytes) and a shared table (B * m * 4 bytes).  N <= 8192,
+ * m <= 8192 and L * B <= 2^27 (so the result takes at most 512 MiB).
+ * Errors before any device work: a NULL pointer, B < 1, m < 1 or an index
+ * outside [0, N): TDA_E_INVALID; N > 8192, m > 8192, L * B > 2^27 or float64
+ * POINT clouds (as tda_greedy_perm, and for its reason): TDA_E_UNSUPPORTED.
+ * Added to ABI 8 (new symbols only; no existing struct changed).
+ */
+#define TDA_RESAMPLE_MAX_OUT (1ll << 27)
+
+typedef struct tda_resample_args {
+    const void *x;          /* (L, N, D) points or (L, N, N) distances, host or device */
+    int32_t dtype;          /* TDA_F32 | TDA_F64 (TDA_F64: distance matrices only)  */
+    int32_t x_on_device;    /* 1: x is a device pointer on `device`                 */
+    int64_t L, N, D;        /* D ignored when is_dist                               */
+    int32_t is_dist;        /* 1: x holds (L, N, N) distance matrices (upper used)  */
+    int32_t device;         /* HIP device ordinal                                   */
+    void *stream;           /* device input is read after it; NULL = null stream    */
+    int64_t B;              /* resamples per layer, >= 1                            */
+    int32_t m;              /* points per resample, 1 .. 8192                       */
+    int32_t idx_per_layer;  /* 0: idx is (B, m), shared by every layer; 1: (L, B, m) */
+    const int32_t *idx;     /* HOST indices into 0 .. N-1                           */
+} tda_resample_args;
+
+typedef struct tda_resample_result {
+    int64_t L, N, B, m;
+    const float *hausdorff;  /* host [L][B]                                          */
+    int32_t device;
+    double device_ms;        /* device time of the call (HIP events)                 */
+} tda_resample_result;
+
+int tda_resample(const tda_resample_args *args, tda_resample_result **out);
+void tda_resample_free(tda_resample_result *r);
+
+/*
  * The other spectral metrics of the reference's metrics.py, on the Gram
  * kernels and the Jacobi kernel of tda_effective_dim (same workspace, same
  * ordering after the caller's stream, same limits: min(N, D) <= 1024 and

@@ -7,7 +7,8 @@ include/tda_rips.h; no CPU fallback.
 """
 import sys as _sys
 
-from . import diagrams, distributed, metrics, synthetic, umap  # noqa: F401
+from . import bootstrap, diagrams, distributed, metrics, synthetic, umap  # noqa: F401
+from .bootstrap import ConfidenceBands, confidence_bands, hausdorff_resamples, resample_indices  # noqa: F401
 from .diagrams import (bottleneck, bottleneck_matrix, heat, heat_kernel_matrix, heat_matrix, persistence_image, persistence_images,  # noqa: F401
                        persistence_landscape, persistence_landscapes, sliced_wasserstein, sliced_wasserstein_kernel, sliced_wasserstein_matrix, wasserstein,
                        wasserstein_matrix)
@@ -53,6 +54,10 @@ __all__ = [
     "heat_matrix",
     "heat_kernel_matrix",
     "layer_features",
+    "confidence_bands",
+    "ConfidenceBands",
+    "resample_indices",
+    "hausdorff_resamples",
     "persistence_landscape",
     "persistence_landscapes",
     "persistence_image",

@@ -187,6 +187,41 @@ class GreedyResult(ctypes.Structure):  # include/tda_rips.h tda_greedy_result
     ]
 
 
+class ResampleArgs(ctypes.Structure):  # include/tda_rips.h tda_resample_args
+    _fields_ = [
+        ("x", ctypes.c_void_p),
+        ("dtype", ctypes.c_int32),
+        ("x_on_device", ctypes.c_int32),
+        ("L", ctypes.c_int64),
+        ("N", ctypes.c_int64),
+        ("D", ctypes.c_int64),
+        ("is_dist", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("stream", ctypes.c_void_p),
+        ("B", ctypes.c_int64),
+        ("m", ctypes.c_int32),
+        ("idx_per_layer", ctypes.c_int32),
+        ("idx", ctypes.c_void_p),  # host int32 (B, m), or (L, B, m) with idx_per_layer
+    ]
+
+
+class ResampleResult(ctypes.Structure):  # include/tda_rips.h tda_resample_result
+    _fields_ = [
+        ("L", ctypes.c_int64),
+        ("N", ctypes.c_int64),
+        ("B", ctypes.c_int64),
+        ("m", ctypes.c_int64),
+        ("hausdorff", _f32p),
+        ("device", ctypes.c_int32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
+TDA_RS_LDS_N = 128  # csrc/resample_kernels.h kRsLdsN: the largest N whose matrix k_resample_hausdorff stages in LDS
+TDA_RS_MAX_POINTS = 8192  # N and m of a tda_resample call
+TDA_RESAMPLE_MAX_OUT = 1 << 27  # resamples (L * B) of one call
+
+
 class SwArgs(ctypes.Structure):  # include/tda_dgm.h tda_sw_args
     _fields_ = [
         ("points", ctypes.c_void_p),
@@ -374,7 +409,7 @@ class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
 # every symbol declared in include/tda_rips.h and include/tda_umap.h
 EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "tda_version", "tda_device_ok",
            "tda_effective_dim", "tda_effective_dim_windows", "tda_matrix_entropy", "tda_greedy_perm", "tda_greedy_free",
-           "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan")
+           "tda_resample", "tda_resample_free", "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan")
 # the entries of include/tda_dgm.h, all of one shape, int entry(const args*, result**) and void free(result*):
 # name -> (entry symbol, free symbol, args struct, result struct)
 DGM_ENTRIES = {
@@ -513,6 +548,10 @@ def lib():
     L.tda_greedy_perm.restype = ctypes.c_int
     L.tda_greedy_free.argtypes = [ctypes.POINTER(GreedyResult)]
     L.tda_greedy_free.restype = None
+    L.tda_resample.argtypes = [ctypes.POINTER(ResampleArgs), ctypes.POINTER(ctypes.POINTER(ResampleResult))]
+    L.tda_resample.restype = ctypes.c_int
+    L.tda_resample_free.argtypes = [ctypes.POINTER(ResampleResult)]
+    L.tda_resample_free.restype = None
     L.tda_umap_transform.argtypes = [ctypes.POINTER(UmapTransformArgs)]
     L.tda_umap_transform.restype = ctypes.c_int
     for entry, free, Args, Result in DGM_ENTRIES.values():

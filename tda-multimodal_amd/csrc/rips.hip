@@ -1674,6 +1674,8 @@ int tda_device_ok(int32_t device) {
 #include "ed_host.h"
 // greedy furthest-point landmarks, ripser.py's n_perm (include/tda_rips.h tda_greedy_perm)
 #include "greedy_host.h"
+// resamples of a layer for bootstrap confidence bands (include/tda_rips.h tda_resample)
+#include "resample_host.h"
 // sliced Wasserstein distances between persistence diagrams (include/tda_dgm.h)
 #include "dgm_host.h"
 // bottleneck distances between persistence diagrams (include/tda_dgm.h)
