@@ -389,6 +389,64 @@ typedef struct tda_spectral_args {
 int tda_matrix_entropy(const tda_spectral_args *args, float *out);        /* out[B * max(W, 1)][n_alpha] */
 int tda_effective_dim_windows(const tda_spectral_args *args, float *out); /* out[B][W] */
 
+/*
+ * Native sweep pipeline: consecutive sweeps of a layer loop in flight at once,
+ * without a host thread of the caller per call.  The pipe owns `depth` worker
+ * threads, one per workspace slot (the top `depth` slots of the device; slot 0
+ * is left to plain calls), coalesces up to `coalesce` consecutive sweeps into
+ * one tda_rips_batch call (their arrays as x_parts) and hands every sweep its
+ * own layers of the call's result.  The caller makes one short call per sweep
+ * (tda_pipe_submit) and one blocking call per result (tda_pipe_wait); a
+ * binding whose interpreter has a global lock never takes it in a worker.
+ *
+ * The pending batch is dispatched when it holds `coalesce` sweeps, when a
+ * sweep with another (L, N, D), dtype, residence or tmpl_id arrives, when one
+ * of its tickets is waited on, and at flush / destroy.  Call n runs on worker
+ * n % depth, so the calls of one slot stay ordered.
+ *
+ * tda_pipe_submit: *tmpl gives every argument of the call but x, dtype,
+ * x_on_device, L, N, D, slot, x_parts and n_parts, which the pipe fills
+ * (TDA_FLAG_ONE_STREAM is the caller's to set in tmpl->flags: each worker then
+ * holds one hardware queue).  The template is copied when a batch starts;
+ * sweeps share a call only under one tmpl_id, so equal ids must mean equal
+ * contents.  Device input must be complete (TDA_FLAG_INPUT_READY in
+ * tmpl->flags): a worker does not order itself after any caller stream.  x and
+ * tmpl->labels must stay valid until the ticket's tda_pipe_wait has returned.
+ * Host input is checked for NaN / infinity by the worker, before the call: the
+ * call then fails with TDA_E_INVALID, "Input contains NaN or infinity.".
+ *
+ * tda_pipe_wait with TDA_PIPE_BLOCK: blocks until the ticket's call has run.
+ * Returns the call's code (with its message in tda_last_error() of the waiting
+ * thread); every ticket of a failed call reports the same error.  On success
+ * *res is the call's result, shared by its *n_sweeps tickets, of which layers
+ * [*lo, *hi) are the ticket's; *call identifies the call (tickets of one call
+ * agree).  TDA_PIPE_POLL never blocks and dispatches nothing; TDA_PIPE_DISPATCH
+ * dispatches the ticket's batch if it is still pending and does not block
+ * either: both return TDA_PIPE_BUSY (with *res NULL) while the call has not run.
+ * The result stays valid until the LAST of the call's tickets is released,
+ * which frees it; never pass it to tda_rips_free.  tda_pipe_release returns the
+ * number of the call's tickets still unreleased (>= 0) or TDA_E_INVALID.
+ * tda_pipe_destroy dispatches what is pending, lets the workers finish, joins
+ * them and frees every result still held; all tickets die with the pipe.
+ * Submit, wait and release may be called from any threads.
+ * Added to ABI 8 (new symbols only; no existing struct changed).
+ */
+typedef struct tda_pipe tda_pipe;
+
+#define TDA_PIPE_POLL 0
+#define TDA_PIPE_BLOCK 1
+#define TDA_PIPE_DISPATCH 2
+#define TDA_PIPE_BUSY 1
+
+int tda_pipe_create(int32_t depth, int32_t coalesce, tda_pipe **out);
+int tda_pipe_submit(tda_pipe *pipe, const tda_rips_args *tmpl, int64_t tmpl_id, const void *x, int64_t L, int64_t N, int64_t D,
+                    int32_t dtype, int32_t x_on_device, uint64_t *ticket);
+int tda_pipe_flush(tda_pipe *pipe);
+int tda_pipe_wait(tda_pipe *pipe, uint64_t ticket, tda_rips_result **res, int64_t *lo, int64_t *hi, int32_t *n_sweeps,
+                  uint64_t *call, int32_t mode);
+int tda_pipe_release(tda_pipe *pipe, uint64_t ticket);
+void tda_pipe_destroy(tda_pipe *pipe);
+
 #ifdef __cplusplus
 }
 #endif

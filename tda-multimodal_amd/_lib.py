@@ -95,6 +95,8 @@ TDA_FLAG_ONE_STREAM = 16
 TDA_FLAG_INPUT_READY = 32
 TDA_MAX_SLOTS = 8
 TDA_MAX_PARTS = 16
+TDA_PIPE_POLL, TDA_PIPE_BLOCK, TDA_PIPE_DISPATCH = 0, 1, 2  # tda_pipe_wait modes
+TDA_PIPE_BUSY = 1  # tda_pipe_wait: the ticket's call has not run yet
 
 
 class UmapArgs(ctypes.Structure):  # include/tda_umap.h
@@ -409,7 +411,8 @@ class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
 # every symbol declared in include/tda_rips.h and include/tda_umap.h
 EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "tda_version", "tda_device_ok",
            "tda_effective_dim", "tda_effective_dim_windows", "tda_matrix_entropy", "tda_greedy_perm", "tda_greedy_free",
-           "tda_resample", "tda_resample_free", "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan")
+           "tda_resample", "tda_resample_free", "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan",
+           "tda_pipe_create", "tda_pipe_submit", "tda_pipe_flush", "tda_pipe_wait", "tda_pipe_release", "tda_pipe_destroy")
 # the entries of include/tda_dgm.h, all of one shape, int entry(const args*, result**) and void free(result*):
 # name -> (entry symbol, free symbol, args struct, result struct)
 DGM_ENTRIES = {
@@ -554,6 +557,22 @@ def lib():
     L.tda_resample_free.restype = None
     L.tda_umap_transform.argtypes = [ctypes.POINTER(UmapTransformArgs)]
     L.tda_umap_transform.restype = ctypes.c_int
+    # the native sweep pipeline (tda_pipe_*): the pipe is an opaque handle, tickets and call ids are uint64
+    _u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.tda_pipe_create.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
+    L.tda_pipe_create.restype = ctypes.c_int
+    L.tda_pipe_submit.argtypes = [ctypes.c_void_p, ctypes.POINTER(RipsArgs), ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                  ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, _u64p]
+    L.tda_pipe_submit.restype = ctypes.c_int
+    L.tda_pipe_flush.argtypes = [ctypes.c_void_p]
+    L.tda_pipe_flush.restype = ctypes.c_int
+    L.tda_pipe_wait.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.POINTER(RipsResult)), _i64p, _i64p, _i32p,
+                                _u64p, ctypes.c_int32]
+    L.tda_pipe_wait.restype = ctypes.c_int
+    L.tda_pipe_release.argtypes = [ctypes.c_void_p, ctypes.c_uint64]
+    L.tda_pipe_release.restype = ctypes.c_int
+    L.tda_pipe_destroy.argtypes = [ctypes.c_void_p]
+    L.tda_pipe_destroy.restype = None
     for entry, free, Args, Result in DGM_ENTRIES.values():
         getattr(L, entry).argtypes = [ctypes.POINTER(Args), ctypes.POINTER(ctypes.POINTER(Result))]
         getattr(L, entry).restype = ctypes.c_int

@@ -1667,6 +1667,64 @@ int tda_device_ok(int32_t device) {
 
 }  // extern "C"
 
+// the native sweep pipeline (include/tda_rips.h tda_pipe_*): the queue of sweep_pipe.h around tda_rips_batch
+#include "sweep_pipe.h"
+
+struct tda_pipe {
+    tda::SweepPipe q;
+    tda_pipe(int depth, int coalesce) : q(depth, coalesce, tda_rips_batch, tda_rips_free, tda_last_error) {}
+};
+
+extern "C" {
+
+int tda_pipe_create(int32_t depth, int32_t coalesce, tda_pipe** out) {
+    if (!out) return fail(TDA_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (depth < 1 || depth > TDA_MAX_SLOTS) return fail(TDA_E_INVALID, "depth must be in [1, TDA_MAX_SLOTS]");
+    if (coalesce < 1 || coalesce > TDA_MAX_PARTS) return fail(TDA_E_INVALID, "coalesce must be in [1, TDA_MAX_PARTS]");
+    *out = new tda_pipe(depth, coalesce);
+    return 0;
+}
+
+int tda_pipe_submit(tda_pipe* pipe, const tda_rips_args* tmpl, int64_t tmpl_id, const void* x, int64_t L, int64_t N, int64_t D,
+                    int32_t dtype, int32_t x_on_device, uint64_t* ticket) {
+    if (!pipe || !tmpl || !ticket) return fail(TDA_E_INVALID, "tda_pipe_submit: a NULL argument");
+    if (x_on_device && !(tmpl->flags & TDA_FLAG_INPUT_READY))
+        return fail(TDA_E_INVALID, "tda_pipe_submit: device input needs TDA_FLAG_INPUT_READY");
+    std::string err;
+    const int rc = pipe->q.submit(*tmpl, tmpl_id, x, L, N, D, dtype, x_on_device, ticket, &err);
+    return rc ? fail(rc, err) : 0;
+}
+
+int tda_pipe_flush(tda_pipe* pipe) {
+    if (!pipe) return fail(TDA_E_INVALID, "pipe is NULL");
+    pipe->q.flush();
+    return 0;
+}
+
+int tda_pipe_wait(tda_pipe* pipe, uint64_t ticket, tda_rips_result** res, int64_t* lo, int64_t* hi, int32_t* n_sweeps,
+                  uint64_t* call, int32_t mode) {
+    if (!pipe || !res || !lo || !hi || !n_sweeps || !call) return fail(TDA_E_INVALID, "tda_pipe_wait: a NULL argument");
+    if (mode < TDA_PIPE_POLL || mode > TDA_PIPE_DISPATCH) return fail(TDA_E_INVALID, "tda_pipe_wait: bad mode");
+    tda::SweepPipe::Waited w = pipe->q.wait(ticket, (tda::SweepPipe::Mode)mode);
+    *res = w.res;
+    *lo = w.lo;
+    *hi = w.hi;
+    *n_sweeps = w.n_sweeps;
+    *call = w.call;
+    return w.rc < 0 ? fail(w.rc, w.err) : w.rc;
+}
+
+int tda_pipe_release(tda_pipe* pipe, uint64_t ticket) {
+    if (!pipe) return fail(TDA_E_INVALID, "pipe is NULL");
+    const int left = pipe->q.release(ticket);
+    return left < 0 ? fail(TDA_E_INVALID, "tda_pipe_release: unknown or released ticket") : left;
+}
+
+void tda_pipe_destroy(tda_pipe* pipe) { delete pipe; }
+
+}  // extern "C"
+
 #include "aux_ws.h"  // the per-device workspace of the entries below, and its locking
 // UMAP embedding (include/tda_umap.h): same library, same error state
 #include "umap_host.h"

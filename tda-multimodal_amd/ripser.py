@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import ctypes
 import warnings
+import weakref
 
 import numpy as np
 
@@ -257,6 +258,41 @@ def _data_ptrs(keeps: list, on_dev: bool) -> list:
     return _lib.hostviews().finite_ptrs(keeps)
 
 
+def _fill_call_args(a, N, maxdim, thresh, distance_matrix, want_dist, stage_times, stage_serial, one_stream, input_ready,
+                    persistence, want_dist64, labels, twonn, discard_fraction, eps):
+    """The arguments of a batch call that do not depend on its input array, into ``a``
+    (ripser_batch's own, and the template of a native SweepPipeline call).  Returns
+    (want_dist as the result must be unpacked, the label codes ``a.labels`` points into)."""
+    a.is_dist = 1 if distance_matrix else 0
+    a.maxdim = int(maxdim)
+    a.thresh = float(thresh) if np.isfinite(thresh) else float("inf")
+    a.modulus = 2
+    a.want_dist = 1 if want_dist else 0
+    a.flags = (_lib.TDA_FLAG_STAGE_TIMES | (_lib.TDA_FLAG_STAGE_SERIAL if stage_serial else 0)) if stage_times else 0
+    if one_stream:
+        a.flags |= _lib.TDA_FLAG_ONE_STREAM
+    if input_ready:
+        a.flags |= _lib.TDA_FLAG_INPUT_READY
+    if not persistence:
+        if maxdim != 0:
+            raise ValueError("persistence=False needs maxdim=0")
+        a.flags |= _lib.TDA_FLAG_NO_PERSISTENCE
+    if want_dist64:  # f64 points: the f64 distance matrix too (ripser.py's dperm2all)
+        a.flags |= _lib.TDA_FLAG_DIST64
+        a.want_dist = 1
+        want_dist = True
+    lab = None
+    if labels is not None:
+        lab = encode_labels(labels, N)
+        a.labels = lab.ctypes.data
+        a.n_label_sets = lab.shape[0]
+    if twonn:
+        a.want_twonn = 1
+        a.twonn_discard = float(discard_fraction)
+        a.twonn_eps = float(eps)
+    return want_dist, lab
+
+
 def ripser_batch(X, maxdim: int = 1, thresh: float = np.inf, distance_matrix: bool = False, device: int = 0,
                  want_dist: bool = False, return_time: bool = False, stage_times: bool = False, labels=None,
                  stage_serial: bool = False, twonn: bool = False, discard_fraction: float = 0.1, eps: float = 1e-10,
@@ -343,37 +379,15 @@ def ripser_batch(X, maxdim: int = 1, thresh: float = np.inf, distance_matrix: bo
         raise ValueError("Distance matrix is not square")
     a.dtype = _lib.TDA_F64 if dtype_is64 else _lib.TDA_F32
     a.L, a.N, a.D = L, N, int(shape[2])
-    a.is_dist = 1 if distance_matrix else 0
-    a.maxdim = int(maxdim)
-    a.thresh = float(thresh) if np.isfinite(thresh) else float("inf")
-    a.modulus = 2
     a.device = int(device)
     a.slot = int(slot)
-    a.want_dist = 1 if want_dist else 0
-    a.flags = (_lib.TDA_FLAG_STAGE_TIMES | (_lib.TDA_FLAG_STAGE_SERIAL if stage_serial else 0)) if stage_times else 0
-    if one_stream:
-        a.flags |= _lib.TDA_FLAG_ONE_STREAM
-    if input_ready:
-        a.flags |= _lib.TDA_FLAG_INPUT_READY
-    if not persistence:
-        if maxdim != 0:
-            raise ValueError("persistence=False needs maxdim=0")
-        a.flags |= _lib.TDA_FLAG_NO_PERSISTENCE
-    if want_dist64:  # f64 points: the f64 distance matrix too (ripser.py's dperm2all)
-        a.flags |= _lib.TDA_FLAG_DIST64
-        a.want_dist = 1
-        want_dist = True
-    lab = None
-    if labels is not None:
-        lab = encode_labels(labels, N)
-        a.labels = lab.ctypes.data
-        a.n_label_sets = lab.shape[0]
-    if twonn:
-        a.want_twonn = 1
-        a.twonn_discard = float(discard_fraction)
-        a.twonn_eps = float(eps)
+    want_dist, lab = _fill_call_args(a, N, maxdim, thresh, distance_matrix, want_dist, stage_times, stage_serial, one_stream,
+                                     input_ready, persistence, want_dist64, labels, twonn, discard_fraction, eps)
     out, info = _call_batch(a, want_dist)
     return (out, info) if return_time else out
+
+
+_RIPSER_BATCH = ripser_batch  # the library's own batch call: what SweepPipeline's native workers stand for
 
 
 class GreedyPerm:
@@ -593,11 +607,66 @@ class _SweepFuture:
         out = self._call.result(timeout)
         if isinstance(out, tuple):  # return_time: (results, info)
             res, info = out
-            return res[self._lo:self._hi], dict(info, coalesced=self._n)
+            call = self._call
+            shared = getattr(call, "_sweep_info", None)
+            if shared is None:  # once per call: its sweeps share the dict
+                shared = call._sweep_info = dict(info, coalesced=self._n)
+            return res[self._lo:self._hi], shared
         return out[self._lo:self._hi]
 
     def done(self):
         return self._call is not None and self._call.done()
+
+
+class _CallTemplate:
+    """The arguments one native pipeline call shares with every call of the same
+    keyword arguments: the C template (``tda_pipe_submit``'s ``tmpl``), what
+    ``_unpack`` needs to read its results, and the label codes it points into.
+    ``given`` holds the caller's own argument objects: the template is found
+    by their identity (``SweepPipeline._args_key``), so they must not be freed,
+    and their ids reused, while it can still be found."""
+
+    __slots__ = ("id", "args", "ref", "want_dist", "n_sets", "return_time", "is_dist", "lab", "given")
+
+    def __init__(self, tid, given, N, device, maxdim=1, thresh=np.inf, distance_matrix=False, want_dist=False,
+                 return_time=False, stage_times=False, labels=None, stage_serial=False, twonn=False, discard_fraction=0.1,
+                 eps=1e-10, want_dist64=False, persistence=True, one_stream=False, input_ready=False, n_perm=None):
+        _check_common(maxdim, 2, False, n_perm, "euclidean")
+        self.given = given
+        a = _lib.RipsArgs()
+        a.device = int(device)
+        self.want_dist, self.lab = _fill_call_args(a, N, maxdim, thresh, distance_matrix, want_dist, stage_times, stage_serial,
+                                                   one_stream, input_ready, persistence, want_dist64, labels, twonn,
+                                                   discard_fraction, eps)
+        self.id, self.args, self.ref = tid, a, ctypes.byref(a)
+        self.n_sets, self.return_time, self.is_dist = int(a.n_label_sets), bool(return_time), bool(distance_matrix)
+
+
+class _NativeFuture:
+    """One sweep submitted to the library's own pipeline (``tda_pipe_*``): it
+    holds the sweep's ticket.  ``result()`` blocks in one C call (no interpreter
+    lock held).  The sweep's input array is kept alive by the pipeline, not by
+    the future (``SweepPipeline._keeps``): a worker reads it whether or not
+    anybody still wants the result."""
+
+    __slots__ = ("_pipe", "_ticket", "_tmpl", "_out", "_exc", "__weakref__")
+
+    def __init__(self, pipe, ticket, tmpl, exc=None):
+        self._pipe, self._ticket, self._tmpl, self._out, self._exc = pipe, ticket, tmpl, None, exc
+
+    def result(self, timeout=None):
+        if self._ticket is not None:
+            self._pipe._resolve(self, timeout)
+        if self._exc is not None:
+            raise self._exc
+        return self._out
+
+    def done(self):
+        return self._ticket is None or self._pipe._poll(self._ticket, _lib.TDA_PIPE_POLL)
+
+    def __del__(self):
+        if self._ticket is not None:  # dropped unread: the pipeline hands the ticket back once its call has run
+            self._pipe._abandon(self._ticket)
 
 
 class SweepPipeline:
@@ -607,8 +676,25 @@ class SweepPipeline:
     chain of latency-bound kernels that leaves most CUs idle, and independent
     sweeps fill them.  ``submit(X)`` returns a future whose ``result()`` is
     ``ripser_batch(X, **kw)``'s; results come back in submission order when
-    waited on in order.  The ctypes call releases the GIL, so the threads
-    overlap their GPU waits.
+    waited on in order.
+
+    Host numpy input, and CUDA tensors submitted with ``input_ready=True``, run
+    on the library's own pipeline (``tda_pipe_*``, csrc/sweep_pipe.h): native
+    worker threads coalesce, call and hand results over, ``submit`` is one
+    short C call and ``result()`` one blocking one, and the interpreter lock is
+    never taken by a worker.  ``run=`` stand-ins and CUDA tensors that must wait
+    for their producer's stream keep the Python path: one host thread per slot
+    whose ctypes call releases the GIL, so the threads overlap their GPU waits.
+    WHICH PATH RUNS: the native workers call the library's ``tda_rips_batch``
+    and nothing else, so the native path is taken only while this module's
+    ``ripser_batch`` is the library's own (``_RIPSER_BATCH``).  Replacing the
+    module attribute (``ripser.ripser_batch = stand_in``: tests/test_api.py
+    does so to record calls, tools/host_timeline.py to time the Python path)
+    is honoured like ``run=stand_in`` -- every call goes through the stand-in on
+    the Python threads.  There is no other switch; ``type(future)`` tells the
+    path (``_NativeFuture`` / ``_SweepFuture``).
+    On the native path ``result()`` of one call's sweeps shares one ``info``
+    dict, and ``result(timeout)`` raises ``TimeoutError`` like the Python path.
 
     coalesce=c (dynamic batching): up to c consecutive submissions of the same
     shape, dtype and arguments run as ONE call over their concatenated layers
@@ -651,6 +737,18 @@ class SweepPipeline:
         self._pkey = None
         self._kw_key = self._args_key(self.kw)
         self._run = run  # the batch call (default ripser_batch; CPU tests pass a stand-in)
+        # the native path (run is None): the library's pipe, made at the first sweep it takes
+        self._np = None
+        self._closed = False
+        self._tmpl = {}  # (argument key, device, N when labels are given) -> _CallTemplate
+        self._tmpl_n = 0  # templates made so far: their ids are never reused
+        # ticket -> (input array, template) until the ticket's call has run: a worker reads the
+        # array (and the template's label codes) whether or not the future is still alive
+        self._keeps = {}
+        self._orphans = []  # tickets of futures dropped unread whose calls had not run yet
+        self._tickets = {}  # ticket -> weak reference to its unread future (close() reads them)
+        self._calls = {}  # call id -> (results, info) of a call some of whose futures are unread
+        self._ulock = threading.RLock()  # one unpack per call (re-entrant: a collected future's __del__ may run under it)
 
     @staticmethod
     def _check_kw(kw):
@@ -688,6 +786,11 @@ class SweepPipeline:
             X = np.asarray(X)
         if X.ndim != 3:
             raise ValueError("X must be (L, N, D)")
+        # a replaced module-level ripser_batch is a stand-in like run= (class docstring, WHICH PATH RUNS)
+        if self._run is None and ripser_batch is _RIPSER_BATCH and (type(X) is np.ndarray or bool(args.get("input_ready"))):
+            return self._submit_native(X, args, kw)
+        if self._np is not None:  # a sweep for the Python path closes the native path's batch
+            _lib.lib().tda_pipe_flush(self._np)
         ev = None
         if _is_torch(X) and X.is_cuda and not args.get("input_ready"):
             # ordered after the SUBMITTING thread's current stream, as of now: the call may be
@@ -711,11 +814,148 @@ class SweepPipeline:
                 self._dispatch_locked()
             return f
 
+    def _template(self, args, kw, device, N):
+        """The native call template of these arguments (made once per argument key).
+        Non-scalar arguments are keyed by identity; the template holds them
+        (``given``), so an id in a key cannot pass to another object.  Per-submit
+        arguments make a template each: past _MAX_TEMPLATES the table starts
+        again (templates of calls still to run are held by ``_keeps``)."""
+        key = (self._args_key(args) if kw else self._kw_key, device, N if args.get("labels") is not None else None)
+        t = self._tmpl.get(key)
+        if t is None:
+            with self._lock:
+                t = self._tmpl.get(key)
+                if t is None:
+                    if len(self._tmpl) >= self._MAX_TEMPLATES:
+                        self._tmpl.clear()
+                    self._tmpl_n += 1
+                    t = self._tmpl[key] = _CallTemplate(self._tmpl_n, args, N, device, **args)
+        return t
+
+    _MAX_TEMPLATES = 64
+
+    def _submit_native(self, X, args, kw):
+        """One sweep into the library's pipe.  A bad submission raises from its
+        future's result(), like a failed call."""
+        if self._closed:
+            raise RuntimeError("cannot submit to a closed SweepPipeline")
+        if self._pending:  # a sweep for the native path closes the Python path's batch
+            self.flush()
+        if self._orphans:
+            self._reap()
+        L = _lib.lib()
+        try:
+            keep, on_dev, device, is64, _ = _prep_input(X, True)
+            Ls, N, D = keep.shape
+            t = self._template(args, kw, device if on_dev else self.device, N)
+            if t.is_dist and D != N:
+                raise ValueError("Distance matrix is not square")
+            if self._np is None:
+                with self._lock:
+                    if self._np is None:
+                        h = ctypes.c_void_p()
+                        _lib.check(L.tda_pipe_create(self.depth, self.coalesce, ctypes.byref(h)))
+                        self._np = h
+            ticket = ctypes.c_uint64()
+            _lib.check(L.tda_pipe_submit(self._np, t.ref, t.id, keep.data_ptr() if on_dev else keep.ctypes.data, Ls, N, D,
+                                         _lib.TDA_F64 if is64 else _lib.TDA_F32, 1 if on_dev else 0, ctypes.byref(ticket)))
+        except Exception as e:
+            return _NativeFuture(self, None, None, e)
+        # from here on a worker may read the array: the pipeline holds it until the call has run
+        self._keeps[ticket.value] = (keep, t)
+        f = _NativeFuture(self, ticket.value, t)
+        self._tickets[f._ticket] = weakref.ref(f)
+        return f
+
+    def _poll(self, ticket, mode) -> bool:
+        """Has the ticket's call run?  (mode TDA_PIPE_DISPATCH sends its batch off first.)"""
+        res, lo, hi = ctypes.POINTER(_lib.RipsResult)(), ctypes.c_int64(), ctypes.c_int64()
+        n, call = ctypes.c_int32(), ctypes.c_uint64()
+        return _lib.lib().tda_pipe_wait(self._np, ticket, ctypes.byref(res), ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(n),
+                                        ctypes.byref(call), mode) != _lib.TDA_PIPE_BUSY
+
+    def _resolve(self, f, timeout=None):
+        """Wait for the future's call, read its result (the first waiter of a
+        call unpacks it for all of them) and hand the ticket back."""
+        import time
+
+        L = _lib.lib()
+        ticket = f._ticket
+        if ticket is None:  # another thread read it meanwhile
+            return
+        if timeout is not None:  # the C wait has no deadline: dispatch, then poll
+            end = time.monotonic() + timeout
+            mode = _lib.TDA_PIPE_DISPATCH
+            while not self._poll(ticket, mode):
+                if time.monotonic() >= end:
+                    raise TimeoutError()
+                mode = _lib.TDA_PIPE_POLL
+                time.sleep(1e-4)
+        res, lo, hi = ctypes.POINTER(_lib.RipsResult)(), ctypes.c_int64(), ctypes.c_int64()
+        n, call = ctypes.c_int32(), ctypes.c_uint64()
+        rc = L.tda_pipe_wait(self._np, ticket, ctypes.byref(res), ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(n),
+                             ctypes.byref(call), _lib.TDA_PIPE_BLOCK)
+        msg = L.tda_last_error().decode(errors="replace") if rc != 0 else None  # this thread's, before any other call
+        with self._ulock:
+            if f._ticket is None:  # another thread read it meanwhile
+                return
+            t = f._tmpl
+            try:
+                if rc != 0:
+                    f._exc = _lib.ERRORS.get(rc, RuntimeError)(msg)
+                else:
+                    ent = self._calls.get(call.value)
+                    if ent is None:
+                        out, info = _unpack(res, t.want_dist, t.n_sets)
+                        info["coalesced"] = n.value
+                        ent = self._calls[call.value] = (out, info)
+                    sl = ent[0][lo.value:hi.value]
+                    f._out = (sl, ent[1]) if t.return_time else sl
+            except Exception as e:
+                f._exc = e
+            finally:
+                f._ticket = None
+                self._tickets.pop(ticket, None)
+                self._keeps.pop(ticket, None)  # the blocking wait returned: the call has run
+                if L.tda_pipe_release(self._np, ticket) <= 0:  # the call's last ticket
+                    self._calls.pop(call.value, None)
+
+    def _abandon(self, ticket):
+        """A future was dropped unread.  Its call may be pending, queued or
+        running, and reads the sweep's array until it is done: the ticket is
+        parked, and handed back (with the array) once a poll says the call ran."""
+        if self._np is None:
+            return
+        self._tickets.pop(ticket, None)
+        self._orphans.append(ticket)
+        self._reap()
+
+    def _reap(self):
+        """Hand back the parked tickets whose calls have run; the others stay."""
+        L = _lib.lib()
+        res, lo, hi = ctypes.POINTER(_lib.RipsResult)(), ctypes.c_int64(), ctypes.c_int64()
+        n, call = ctypes.c_int32(), ctypes.c_uint64()
+        with self._ulock:
+            if self._np is None:
+                return
+            parked, self._orphans = self._orphans, []
+            for ticket in parked:
+                rc = L.tda_pipe_wait(self._np, ticket, ctypes.byref(res), ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(n),
+                                     ctypes.byref(call), _lib.TDA_PIPE_POLL)
+                if rc == _lib.TDA_PIPE_BUSY:
+                    self._orphans.append(ticket)
+                    continue
+                self._keeps.pop(ticket, None)
+                if L.tda_pipe_release(self._np, ticket) <= 0:
+                    self._calls.pop(call.value, None)
+
     def flush(self):
         """Dispatch the sweeps still waiting for a full batch."""
         with self._lock:
             if self._pending:
                 self._dispatch_locked()
+        if self._np is not None:
+            _lib.lib().tda_pipe_flush(self._np)
 
     def _dispatch_pending(self, fut):
         with self._lock:
@@ -754,6 +994,31 @@ class SweepPipeline:
         self.flush()
         for e in self._ex:
             e.shutdown(wait=True)
+        self._closed = True
+        if self._np is not None:
+            # futures not read yet keep their results: read them now, the pipe takes every ticket with it
+            for ref in list(self._tickets.values()):
+                f = ref()
+                if f is not None and f._ticket is not None:
+                    self._resolve(f)
+            self._destroy()
+
+    def _destroy(self):
+        """Destroy the pipe: it runs what is still pending or queued and joins its
+        workers, and only then do the arrays those calls read go."""
+        with self._ulock:
+            h, self._np = self._np, None
+        if h is not None:
+            _lib.lib().tda_pipe_destroy(h)
+        self._orphans = []
+        self._keeps.clear()
+        self._calls.clear()
+
+    def __del__(self):
+        # never closed.  No future is alive (each holds the pipeline), but calls of futures dropped
+        # unread may still be pending or running: _keeps holds their arrays until the workers are joined
+        if getattr(self, "_np", None) is not None:
+            self._destroy()
 
     def __enter__(self):
         return self
