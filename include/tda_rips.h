@@ -343,6 +343,95 @@ int tda_resample(const tda_resample_args *args, tda_resample_result **out);
 void tda_resample_free(tda_resample_result *r);
 
 /*
+ * The permutation test between groups of diagrams (Robinson and Turner 2017,
+ * "Hypothesis testing for topological data analysis") on the GPU.  Inputs, all
+ * on the host: w, an (S, S) float64 matrix of the q-th powers of the pairwise
+ * distances; obs[S], the observed group codes in [0, G); lab[B][S], B
+ * relabellings, each a permutation of obs.  With n_g the size of group g the
+ * weight is c_g = 1 / (2 n_g (n_g - 1)): one rounded division of 1.0 by the
+ * product, which is exact in float64.  For a labelling l:
+ *     col_j = sum over i = 0, 1, ..., S-1 in that order, starting from +0.0,
+ *             of w[i][j] where l_i == l_j        (one rounded addition each;
+ *             an unselected i adds nothing or +0.0: the same bits, as col_j
+ *             is never -0.0)
+ *     t_j   = c[l_j] * col_j                     (one rounded product, never
+ *             fused with an addition)
+ *     T(l)  = 64 partial sums, the k-th over t_j for j = k, k+64, k+128, ...
+ *             in that order from +0.0 (a lane without a column holds +0.0),
+ *             then added pairwise: lanes k and k^1, then k^2, k^4, k^8, k^16,
+ *             k^32
+ * the statistic sigma^2 = sum_g c_g sum_{i, j in g} d(X_i, X_j)^q of the
+ * paper over ordered pairs, in the reduction shape of tda_heat_kernel.  The
+ * call returns t_obs = T(obs), null[b] = T(lab[b]), count = #{b : null[b] <=
+ * t_obs} and pvalue = (1 + count) / (B + 1) (one float64 division; the form
+ * of Phipson and Smyth 2010, never 0).
+ * Promised, bit for bit:
+ *  1. T depends on the partition only.  col_j selects by equality with l_j, so
+ *     it is a function of the SET of diagrams grouped with j and of nothing
+ *     else; c[l_j] depends on the size of that set only; the order of every
+ *     addition is fixed by i and j, never by a group code.  Two labellings
+ *     that split the diagrams into the same sets, two equal-sized groups
+ *     swapped included, give the same bits, and such a row of lab always
+ *     counts as <= t_obs.
+ *  2. null[b] depends on neither B, the row's position in lab, the launch
+ *     shape, which kernel ran, nor the run (no atomics, no order left open).
+ *  3. Everything equals the numpy restatement tests/perm_ref.py.
+ * Not promised: independence of the ORDER of the diagrams.  Permuting the
+ * rows and columns of w and the labels together permutes the additions.  The
+ * bound, as for tda_heat_kernel: every term is non-negative, so every partial
+ * sum is at most the final one and an addition's error is at most u (u =
+ * 2^-53) times the part of T that passes through it.  A term w[i][j] passes
+ * through at most n - 2 inexact additions of col_j (n the size of j's group,
+ * at most S - 2: the diagonal term +0.0 and the first addition onto +0.0 are
+ * exact), one product, ceil(S / 64) - 1 inexact lane additions and 6
+ * butterfly additions.  To first order in u,
+ *     |T - T_exact| <= (n_max + 3 + ceil(S / 64)) u T
+ *                   <= S u T + 7 u T   for S <= 384 (ceil(S / 64) <= 6),
+ * and at most S u T + 33 u T at S = 2048.  Two orders of the same data differ
+ * by at most twice that.
+ * Checked on the host, before any device work, in this order: a NULL pointer,
+ * S < 2, B < 1, G < 2 or reserved != 0: TDA_E_INVALID.  S > TDA_PERM_MAX_S,
+ * G > TDA_PERM_MAX_GROUPS or B * S > TDA_PERM_MAX_TABLE: TDA_E_UNSUPPORTED.
+ * Then TDA_E_INVALID, the message naming the first offending index, for a w
+ * entry that is not finite or is negative, a diagonal entry that is not +0.0,
+ * w[i][j] and w[j][i] that differ in bits, an obs code >= G, a group with
+ * fewer than 2 members, and a row of lab whose label histogram is not that of
+ * obs.  After that the kernels read in bounds by construction.
+ * The call runs on a stream and a per-device workspace of its own (no slot's,
+ * nothing captured into a graph), which holds w, the weights, the table with
+ * obs as one more row (B * S + S bytes) and the B + 1 statistics, and
+ * synchronises before it returns.
+ * Added to ABI 8 (new symbols only; no existing struct changed).
+ */
+#define TDA_PERM_MAX_S 2048
+#define TDA_PERM_MAX_GROUPS 64
+#define TDA_PERM_MAX_TABLE (1ll << 27)
+
+typedef struct tda_perm_args {
+    const double *w;     /* HOST (S, S): symmetric in bits, +0.0 diagonal, finite, >= 0 */
+    const uint8_t *obs;  /* HOST [S]: observed group codes in [0, G)                    */
+    const uint8_t *lab;  /* HOST [B][S]: every row a permutation of obs                 */
+    int64_t S;           /* diagrams, 2 .. TDA_PERM_MAX_S                               */
+    int64_t B;           /* relabellings, >= 1, B * S <= TDA_PERM_MAX_TABLE             */
+    int32_t G;           /* groups, 2 .. TDA_PERM_MAX_GROUPS, each of >= 2 members      */
+    int32_t device;      /* HIP device ordinal                                          */
+    int32_t reserved;    /* must be 0                                                   */
+} tda_perm_args;
+
+typedef struct tda_perm_result {
+    int64_t S, B;
+    double t_obs;        /* T(obs)                                                      */
+    const double *null;  /* host [B]: T(lab[b])                                         */
+    int64_t count;       /* #{b : null[b] <= t_obs}                                     */
+    double pvalue;       /* (1 + count) / (B + 1)                                       */
+    int32_t device;
+    double device_ms;    /* device time of the call (HIP events)                        */
+} tda_perm_result;
+
+int tda_permutation_test(const tda_perm_args *args, tda_perm_result **out);
+void tda_perm_free(tda_perm_result *r);
+
+/*
  * The other spectral metrics of the reference's metrics.py, on the Gram
  * kernels and the Jacobi kernel of tda_effective_dim (same workspace, same
  * ordering after the caller's stream, same limits: min(N, D) <= 1024 and

@@ -7,11 +7,12 @@ include/tda_rips.h; no CPU fallback.
 """
 import sys as _sys
 
-from . import bootstrap, diagrams, distributed, metrics, synthetic, umap  # noqa: F401
+from . import bootstrap, diagrams, distributed, hypothesis, metrics, synthetic, umap  # noqa: F401
 from .bootstrap import ConfidenceBands, confidence_bands, hausdorff_resamples, resample_indices  # noqa: F401
 from .diagrams import (bottleneck, bottleneck_matrix, heat, heat_kernel_matrix, heat_matrix, persistence_image, persistence_images,  # noqa: F401
                        persistence_landscape, persistence_landscapes, sliced_wasserstein, sliced_wasserstein_kernel, sliced_wasserstein_matrix, wasserstein,
                        wasserstein_matrix)
+from .hypothesis import PermutationTest, diagram_permutation_test, label_permutations, permutation_test  # noqa: F401
 from .metrics import (compute_effective_dimensionality, compute_fixed_window_ed, compute_fixed_window_id,  # noqa: F401
                       compute_intrinsic_dimensionality, matrix_entropy, matrix_entropy_profile)
 from ._lib import BOTTLENECK_EXPORTS, DGM_EXPORTS, EXPORTS, HEAT_EXPORTS, LIB_PATH, VECTOR_EXPORTS, WASSERSTEIN_EXPORTS, build, lib  # noqa: F401
@@ -58,6 +59,10 @@ __all__ = [
     "ConfidenceBands",
     "resample_indices",
     "hausdorff_resamples",
+    "permutation_test",
+    "diagram_permutation_test",
+    "label_permutations",
+    "PermutationTest",
     "persistence_landscape",
     "persistence_landscapes",
     "persistence_image",

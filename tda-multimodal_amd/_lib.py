@@ -219,6 +219,37 @@ class ResampleResult(ctypes.Structure):  # include/tda_rips.h tda_resample_resul
     ]
 
 
+class PermArgs(ctypes.Structure):  # include/tda_rips.h tda_perm_args
+    _fields_ = [
+        ("w", ctypes.c_void_p),  # host float64 (S, S)
+        ("obs", ctypes.c_void_p),  # host uint8 (S,)
+        ("lab", ctypes.c_void_p),  # host uint8 (B, S)
+        ("S", ctypes.c_int64),
+        ("B", ctypes.c_int64),
+        ("G", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PermResult(ctypes.Structure):  # include/tda_rips.h tda_perm_result
+    _fields_ = [
+        ("S", ctypes.c_int64),
+        ("B", ctypes.c_int64),
+        ("t_obs", ctypes.c_double),
+        ("null", ctypes.POINTER(ctypes.c_double)),
+        ("count", ctypes.c_int64),
+        ("pvalue", ctypes.c_double),
+        ("device", ctypes.c_int32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
+TDA_PERM_MAX_S = 2048  # diagrams of a tda_permutation_test call
+TDA_PERM_MAX_GROUPS = 64
+TDA_PERM_MAX_TABLE = 1 << 27  # entries (B * S) of one call's label table
+TDA_PERM_LDS_S = 128  # csrc/perm_kernels.h kPermLdsS: the largest S whose matrix k_perm_resident stages in LDS
+TDA_PERM_ROWS = 8  # csrc/perm_kernels.h kPermR: labellings of one k_perm_tiled workgroup
 TDA_RS_LDS_N = 128  # csrc/resample_kernels.h kRsLdsN: the largest N whose matrix k_resample_hausdorff stages in LDS
 TDA_RS_MAX_POINTS = 8192  # N and m of a tda_resample call
 TDA_RESAMPLE_MAX_OUT = 1 << 27  # resamples (L * B) of one call
@@ -411,7 +442,7 @@ class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
 # every symbol declared in include/tda_rips.h and include/tda_umap.h
 EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "tda_version", "tda_device_ok",
            "tda_effective_dim", "tda_effective_dim_windows", "tda_matrix_entropy", "tda_greedy_perm", "tda_greedy_free",
-           "tda_resample", "tda_resample_free", "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan",
+           "tda_resample", "tda_resample_free", "tda_permutation_test", "tda_perm_free", "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan",
            "tda_pipe_create", "tda_pipe_submit", "tda_pipe_flush", "tda_pipe_wait", "tda_pipe_release", "tda_pipe_destroy")
 # the entries of include/tda_dgm.h, all of one shape, int entry(const args*, result**) and void free(result*):
 # name -> (entry symbol, free symbol, args struct, result struct)
@@ -555,6 +586,10 @@ def lib():
     L.tda_resample.restype = ctypes.c_int
     L.tda_resample_free.argtypes = [ctypes.POINTER(ResampleResult)]
     L.tda_resample_free.restype = None
+    L.tda_permutation_test.argtypes = [ctypes.POINTER(PermArgs), ctypes.POINTER(ctypes.POINTER(PermResult))]
+    L.tda_permutation_test.restype = ctypes.c_int
+    L.tda_perm_free.argtypes = [ctypes.POINTER(PermResult)]
+    L.tda_perm_free.restype = None
     L.tda_umap_transform.argtypes = [ctypes.POINTER(UmapTransformArgs)]
     L.tda_umap_transform.restype = ctypes.c_int
     # the native sweep pipeline (tda_pipe_*): the pipe is an opaque handle, tickets and call ids are uint64
