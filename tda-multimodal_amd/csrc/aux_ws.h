@@ -91,14 +91,6 @@ int aux_lds_attr(AuxWs& w, const void* fn, size_t bytes) {
     return 0;
 }
 
-// consecutive 256-byte-aligned offsets into a buffer
-struct Carve {
-    size_t o = 0;
-    size_t take(size_t bytes) {
-        const size_t r = o;
-        o = align_up(o + bytes, 256);
-        return r;
-    }
-};
+// (an entry's buffer is cut with Carve, rips_plan.h)
 
 }  // namespace

@@ -5,6 +5,11 @@
 // One call processes a batch of L layers (the reference's 32-layer sweep,
 // debug_tda_pipeline.py:92-150) with ~8 + 3*maxdim kernel launches on one
 // stream and a single host synchronisation at the end.
+//
+// The plan of a call -- which reducer and distance kernels run, every dynamic-LDS size and every
+// offset into the device workspace -- is host arithmetic in rips_plan.h (HIP-free, with the
+// structs and limits it shares with the kernels in rips_shapes.h; tests/test_rips_plan_cpu.py
+// pins it); the launches that read it are in rips_enqueue.h.
 #include <hip/hip_runtime.h>
 #include <execinfo.h>
 #include <link.h>
@@ -31,6 +36,7 @@
 #include "rips_reduce_par.h"
 #include "rips_reduce_small.h"
 #include "rips_retry.h"
+#include "rips_plan.h"
 
 using namespace tda;
 
@@ -71,418 +77,6 @@ int fail(int code, const std::string& msg) {
         hipError_t e_ = (x);                                                                      \
         if (e_ != hipSuccess) return fail(TDA_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
     } while (0)
-
-inline uint64_t next_pow2(uint64_t x) {
-    uint64_t p = 1;
-    while (p < x) p <<= 1;
-    return p;
-}
-inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-inline int ilog2(uint64_t x) {
-    int r = 0;
-    while ((1ull << (r + 1)) <= x) ++r;
-    return r;
-}
-
-// Test / A-B knobs (TDA_REDUCE, TDA_PAR, TDA_CHAIN, TDA_DIST, TDA_ORDER, ...)
-// force a kernel variant or a launch shape.  The library honours them only
-// when TDA_TEST_OVERRIDES=1 is set as well, so a stray variable in a user's
-// environment cannot change the reducer (tests/conftest.py sets the gate).
-const char* test_env(const char* name) {
-    const char* g = getenv("TDA_TEST_OVERRIDES");
-    return (g && g[0] == '1' && !g[1]) ? getenv(name) : nullptr;
-}
-bool test_env_is(const char* name, const char* val) {
-    const char* m = test_env(name);
-    return m && !strcmp(m, val);
-}
-
-constexpr uint64_t kRCapMax = 1ull << 22;    // residual columns per layer and dim
-constexpr uint64_t kPCapMax = 1ull << 16;    // emitted pairs per layer and dim (H>=1)
-constexpr int kLdsMax = 160 * 1024;
-constexpr int kSmallN = 64;                  // one-wave H0 + LDS-resident reduction up to here
-constexpr int kAppLdsMaxN = 128;             // k_apparent stages the distance matrix in LDS up to here
-constexpr int kBigMinN = 256;                // large-N reducer above this N (global mode)
-constexpr int64_t kDistMfmaMinD = 32;        // k_distance_mfma (FP64 MFMA Gram tiles) from this D up
-constexpr unsigned kParGrid = 512;           // k_reduce_par workgroups at most (pool sizing): two 72-KB-LDS workgroups per CU
-// default: one per CU -- the longest column is the critical path and runs
-// faster without a second workgroup on its CU (r02, tools/ab_pargrid.sh:
-// grid144 10.5 -> 8.5 ms, torus1024 61 -> 58.5 ms at 256 vs 512)
-constexpr unsigned kParGridDefault = 256;
-// column cap of k_reduce_par: keys above birth + f * thresh are never stored.  f = 0.5 keeps
-// 35 % of the keys of torus1024's longest column (whose pivot is at birth + 0.35 thresh; the
-// largest H1 persistence of the torus seeds, grid144 and the sweep clouds is <= 0.38 thresh); a
-// cap that is too small costs one uncapped re-run of the call, remembered for the shape.
-// TDA_PAR_CAPF (tests) overrides it (0 = off).
-float par_capf() {
-    const char* e = test_env("TDA_PAR_CAPF");
-    return e ? (float)atof(e) : 0.5f;
-}
-unsigned par_grid_size() {
-    const char* g = test_env("TDA_PAR_GRID");
-    const unsigned v = g ? (unsigned)atoi(g) : kParGridDefault;
-    return v < 1 ? 1 : (v > kParGrid ? kParGrid : v);
-}
-
-// ------------------------------------------------------------------ plan
-struct Plan {
-    int64_t L = 0, N = 0, D = 0;
-    int maxdim = 0, dtype = 0, is_dist = 0;
-    bool want64 = false;  // TDA_FLAG_DIST64: f64 distances of f64 points as well (dperm2all)
-    uint64_t ncand[4] = {0}, piv_words[4] = {0}, rcap[4] = {0}, pcap[4] = {0};
-    uint64_t mst_words = 0, max_rcap = 0, rmap_stride = 0, vpool_cap = 0, wcap_g = 0, vcap_g = 0, sstride = 0;
-    bool lds_mode = false;
-    bool big = false;  // k_reduce_big (1024-thread radix-heap reduction) instead of one wave per layer
-    bool par = false;  // H1 on k_reduce_par (many columns in flight), k_reduce_big for H2 / fallback
-    bool par2 = false;    // H2 on k_reduce_par as well (N <= 568: 32-bit tetrahedron indices)
-    bool packed = false;  // k_reduce_par keys carry packed vertices + apparent facet (N <= 1024)
-    bool wide = false;    // H2 on k_reduce_big with edge-code keys (tetrahedron indices > 32 bits)
-    uint64_t ecap = 0;    // per-layer stride of the sorted edge lengths
-    size_t o_dsort = 0, o_dtmp = 0, o_dcode = 0;
-    int dsplit = 1;       // K slices of k_distance_mfma (1: no split)
-    bool gram_layer = false;  // N <= 144, f32: k_gram_layer (whole upper triangle per workgroup) + combine
-    size_t o_gpart = 0, o_npart = 0, o_d64 = 0;
-    size_t o_bcomp = 0, o_bcheap = 0, o_bctl = 0;  // Borůvka H0 state (N > kH0WaveMaxN)
-    bool serial_tables = false;  // HBM working tables of k_reduce_all (global mode) / k_reduce_big
-    uint64_t ostride = 0, rec_cap = 0, rpool_cap = 0, bpool_cap = 0, rq_cap = 0;
-    size_t o_pctl = 0, o_pitem = 0, o_pokey = 0, o_poval = 0, o_colpiv = 0, o_prec = 0, o_prpool = 0, o_pbpool = 0, o_prq = 0, o_pdbg = 0;
-    bool dense = false;  // N <= 64: dense-bitmap H1 chain + column-parallel H2 phase 1 (rips_reduce_small.h)
-    int dK = 0;          // dense H1 bitmap words per lane (a k_h1_chain instantiation)
-    uint32_t inv_stride = 0;  // rank -> edge table stride (C(N,3) rounded up)
-    uint32_t tri_stride = 0;  // triangle -> rank table stride (C(N,3) rounded up)
-    bool fast = false;        // rank_of + inv32 tables exist (k_h1_chain FAST / TABLE)
-    int cmode = 0;            // k_h1_chain MODE: kChainGeneral / kChainFast / kChainTable
-    uint32_t cob_stride = 0;  // per-layer coboundary table (TABLE): E * N rounded up
-    uint32_t chain_lds = 0;   // dynamic LDS of k_h1_chain
-    uint32_t p1_lds = 0;      // dynamic LDS of k_h2_phase1
-    int p1_waves = 1;         // waves per k_h2_phase1 block
-    uint32_t n2p = 0;         // stride of the per-layer edge-class table (N * N rounded up)
-    uint32_t bm_words = 0;    // tetrahedron membership bitmap of k_h2_phase1 (words)
-    uint32_t prep_lds = 0;    // dynamic LDS of k_prep_edges
-    ReduceAllCfg rcfg = {};
-    // byte offsets in the device workspace
-    size_t o_x = 0, o_dist = 0, o_stats = 0, o_mst = 0, o_piv[4] = {0}, o_resid[4] = {0}, o_tmp = 0, o_rmk = 0, o_rmv = 0,
-           o_voff = 0, o_vlen = 0, o_vpool = 0, o_wk = 0, o_wt = 0, o_wp = 0, o_wl = 0, o_vk = 0, o_vt = 0, o_vp = 0, o_vl = 0, o_bref = 0, o_recs = 0, o_cls2 = 0, o_cls = 0, o_res1 = 0, o_inv32 = 0, o_rof = 0, o_inv = 0, o_epos = 0, o_cobt = 0, o_eM = 0, o_necnt = 0, o_p1next = 0, o_p1k = 0, o_p1i = 0, o_p1x = 0, o_roff2 = 0, o_rlen2 = 0, o_rpool2 = 0, o_p1used = 0,
-           o_hsig = 0, o_rowmax = 0, o_pairs[4] = {0}, o_h0s = 0,
-           o_fk = 0, o_fv = 0, o_pptr = 0, o_pcap = 0, o_outoff = 0, total = 0;
-    size_t memset_lo = 0, memset_hi = 0;  // zeroed every call: stats .. pivbits
-    // H2 pivot bitmap too large to memset every call (>= 2 GB: C(N, 4) / 8 B per layer, 91 GB at
-    // N = 2048): kept zero between calls by k_clear_words over the words k_apparent<2> lists
-    bool piv2_sparse = false;
-    uint64_t clr_cap = 0;
-    size_t o_clr2 = 0;
-};
-
-bool getenv_is(const char* name, const char* val) {
-    const char* m = getenv(name);
-    return m && !strcmp(m, val);
-}
-
-
-// pivots per column before a reduction kernel gives up (ERR_STEP_LIMIT): an
-// exit guarantee, far above any real column (torus1024: < 2^15)
-uint64_t step_limit() {
-    const char* sl = test_env("TDA_STEP_LIMIT");
-    return sl ? strtoull(sl, nullptr, 10) : (1ull << 26);
-}
-
-// LDS carve of k_reduce_all (mirrors the kernel): [16][dist][map H1][per-dim:
-// map H2 (dim 2 only) + W (log 8 B + index 16 B per entry) + pivot bitmap]
-ReduceAllCfg reduce_cfg(int n, int maxdim, const uint64_t* piv_words, bool lds_mode) {
-    ReduceAllCfg c{};
-    auto al = [](uint64_t x) { return (x + 15) & ~15ull; };
-    const uint32_t mapcap = 1024;
-    c.dist_lds = lds_mode ? 1 : 0;
-    const uint64_t prefix = 16 + (c.dist_lds ? al(4ull * n * n) : 0) + 12ull * mapcap;
-    uint64_t need = prefix;
-    for (int d = 1; d <= maxdim; ++d) {
-        Reduce2Cfg& r = c.dim[d];
-        r.rmap_lds_cap = mapcap;
-        const uint64_t map = d == 2 ? 12ull * mapcap : 0;
-        const uint64_t piv = al(4ull * piv_words[d]);
-        if (!lds_mode) {
-            r.wcap = 0;
-            r.piv_lds = 0;
-            need = std::max<uint64_t>(need, prefix + map);
-            continue;
-        }
-        r.wcap = 4096;
-        r.piv_lds = 1;
-        auto bytes = [&]() { return prefix + map + 24ull * r.wcap + r.wcap + (r.piv_lds ? piv : 0); };
-        if (bytes() > (uint64_t)kLdsMax) r.piv_lds = 0;
-        while (r.wcap > 1024 && bytes() > (uint64_t)kLdsMax) r.wcap >>= 1;
-        need = std::max<uint64_t>(need, bytes());
-    }
-    c.bytes = (uint32_t)need;
-    c.step_limit = step_limit();
-    return c;
-}
-
-// Which kernels turn (N, D) point clouds into distances (launch_point_distances, rips_enqueue.h):
-// the scalar k_distance, or from D = kDistMfmaMinD up the FP64 MFMA Gram tiles, as K slices
-// (dsplit > 1: partial Grams + k_distance_combine) when the tiles alone leave CUs idle: aim at
-// ~3 workgroups per CU, at least 4 K chunks per slice (TDA_DIST_SPLIT=n forces n).  The slice
-// count fixes the f64 summation order, so it depends on (N, D) only -- sized for the reference's
-// 32-layer sweep (debug_tda_pipeline.py:92), never on a call's L: a layer's distances (and so
-// its diagram) are the same in a single call, a batch and every multi-GPU shard.
-struct DistSel {
-    bool mfma = false;
-    int dsplit = 1;           // K slices of k_distance_mfma (1: no split)
-    bool gram_layer = false;  // N <= 144, f32: k_gram_layer (whole upper triangle per workgroup) + combine
-    bool partials() const { return gram_layer || dsplit > 1; }  // gpart / npart buffers are needed
-};
-// D >= 32 (raw activations): Gram tiles on the FP64 matrix cores; TDA_DIST=scalar|mfma forces one (tests)
-bool dist_use_mfma(int64_t D) { return test_env_is("TDA_DIST", "mfma") || (D >= kDistMfmaMinD && !test_env_is("TDA_DIST", "scalar")); }
-DistSel dist_select(uint64_t N, int64_t D, int dtype, bool is_dist) {
-    DistSel s;
-    s.mfma = !is_dist && dist_use_mfma(D);
-    if (s.mfma && dtype == TDA_F32 && N <= (uint64_t)kGlMaxN && !test_env_is("TDA_DIST", "tiles")) {
-        // whole-layer Gram (k_gram_layer): K slices so that a 32-layer sweep runs two
-        // workgroups per CU (512), at least 8 chunks each -- again from (N, D) only.
-        // raw4096: 16 slices 94 us + combine 26 us; 8: 130 + 15; 32: 101 + 35 (r03)
-        const uint64_t chunks = ((uint64_t)D + kDmKC - 1) / kDmKC;
-        uint64_t sp = std::min<uint64_t>(16, std::max<uint64_t>(1, chunks / 8));
-        if (const char* e = test_env("TDA_DIST_SPLIT")) sp = std::max(1, atoi(e));
-        s.dsplit = (int)sp;
-        s.gram_layer = true;
-    } else if (s.mfma) {
-        constexpr uint64_t kSplitRefL = 32;
-        const uint64_t nt = (N + kDmT - 1) / kDmT, tiles = nt * (nt + 1) / 2 * kSplitRefL, chunks = ((uint64_t)D + kDmKC - 1) / kDmKC;
-        uint64_t sp = std::min<uint64_t>(8, std::max<uint64_t>(1, (768 + tiles - 1) / tiles));
-        sp = std::min<uint64_t>(sp, std::max<uint64_t>(1, chunks / 4));
-        if (const char* e = test_env("TDA_DIST_SPLIT")) sp = std::max(1, atoi(e));
-        s.dsplit = (int)sp;
-    }
-    return s;
-}
-
-int make_plan(Plan& p, const Attempt& at) {
-    const bool force_global = at.force_global, force_big = at.force_big;
-    const int scale = at.scale, no_par = at.no_par;
-    const uint64_t N = (uint64_t)p.N, L = (uint64_t)p.L;
-    p.mst_words = (binom(N, 2) + 31) / 32 + 1;
-    for (int d = 1; d <= p.maxdim; ++d) {
-        p.ncand[d] = binom(N, d + 1);
-        p.piv_words[d] = (binom(N, d + 2) + 31) / 32 + 1;
-        p.rcap[d] = std::max<uint64_t>(1, std::min(p.ncand[d], kRCapMax));
-        p.pcap[d] = std::max<uint64_t>(16, std::min(p.ncand[d], kPCapMax));
-        p.max_rcap = std::max(p.max_rcap, p.rcap[d]);
-    }
-    p.pcap[0] = N + 1;
-    p.max_rcap = std::max<uint64_t>(p.max_rcap, 1);
-    p.rmap_stride = next_pow2(2 * p.max_rcap + 16);
-    // capacity retries: `scale` grows the parallel reducer's pools up to 16x (kMaxParScale); the
-    // other work buffers (serial reducers) grow up to 4x
-    const int s2 = std::min(scale, 2);
-    p.vpool_cap = std::min<uint64_t>(std::max<uint64_t>(1ull << 16, 32 * p.max_rcap), 1ull << 27) << s2;
-    p.lds_mode = p.N <= kSmallN && !force_global;
-    p.rcfg = reduce_cfg((int)N, p.maxdim, p.piv_words, p.lds_mode);
-    p.wcap_g = (N <= 256 ? 1ull << 17 : (N <= 640 ? 1ull << 21 : 1ull << 23)) << (2 * s2);
-    {
-        const char* m = test_env("TDA_REDUCE");
-        // measured (r01): one wave per layer beats the serial radix heap up to
-        // N = 256 (grid144 md2 20.6 vs 26.8 ms); measured (r02): the parallel
-        // reducer k_reduce_par beats both at every N > 64, H1 and H2, L = 1 and
-        // 32 (tools/ab_reduce.py: grid144 md2 L=32 24.1 -> 6.8 ms, torus256
-        // md2 L=32 926 -> 50 ms).  After a parallel abort (no_par) the old rule.
-        const bool want_wave = m && !strcmp(m, "wave"), want_big = m && !strcmp(m, "big"), want_par = m && !strcmp(m, "par");
-        const bool par_ok = no_par < 2 && p.maxdim >= 1 && !test_env_is("TDA_PAR", "0");
-        p.big = !p.lds_mode && (force_big || want_big || want_par || (!want_wave && (p.N > kBigMinN || par_ok)));
-        // TDA_PAR=0: H1 on the serial k_reduce_big as well (comparison / debugging)
-        p.par = p.big && p.maxdim >= 1 && no_par < 2 && !test_env_is("TDA_PAR", "0");
-        p.packed = p.N <= 1024;
-        // C(N, 4) >= 2^32 (N > 568): the 32-bit index word of the H2 pivot keys
-        // overflows; TDA_H2_WIDE=1 forces the wide keys on any big-path N (tests)
-        p.wide = p.big && p.maxdim >= 2 && (binom(N, 4) >= (1ull << 32) || test_env_is("TDA_H2_WIDE", "1"));
-        // TDA_PAR2=0: H2 on the serial radix-heap kernel after a parallel H1
-        p.par2 = p.par && p.maxdim >= 2 && no_par < 1 && !test_env_is("TDA_PAR2", "0");
-        p.dense = p.lds_mode && p.maxdim >= 1 && p.N <= kDenseMaxN && p.N >= 3 && !want_wave;
-    }
-    if (p.dense) {  // carve of rips_reduce_small.h (h1_chain / h2_phase1), mirrored here
-        const uint64_t E = binom(N, 2), T3 = binom(N, 3);
-        const int kneed = (int)std::max<uint64_t>(1, (((T3 + 31) / 32) + 63) / 64);
-        p.dK = 0;
-        for (int k : kChainKs)
-            if (k >= kneed) {
-                p.dK = k;
-                break;
-            }
-        p.inv_stride = (uint32_t)align_up(T3, 8);
-        auto al = [](uint64_t x) { return (x + 15) & ~15ull; };
-        const uint64_t pre = 16 + al(4 * N * N);
-        const uint64_t WP = 64ull * p.dK;
-        p.tri_stride = (uint32_t)align_up(T3, 8);
-        const uint64_t tail = 2 * al(4 * WP) + al(4 * p.piv_words[1]) + al(8ull * kChainMaxCols) + al(2ull * kChainMaxCols);
-        const uint64_t fast_lds = pre + al(2ull * p.tri_stride) + al(4ull * p.inv_stride) + tail;
-        p.cob_stride = (uint32_t)align_up(E * N, 8);
-        const uint64_t table_lds = 16 + al(2ull * p.cob_stride) + al(2ull * p.inv_stride) + al(4 * WP) + al(4 * p.piv_words[1]) +
-                                   al(8ull * kChainMaxCols) + al(2ull * kChainMaxCols);
-        // TDA_CHAIN=general|fast forces a slower variant (tests)
-        const bool want_gen = test_env_is("TDA_CHAIN", "general"), want_fast = test_env_is("TDA_CHAIN", "fast");
-        p.cmode = kChainGeneral;
-        if (!want_gen && p.dK <= kChainFastMaxK) {
-            if (!want_fast && table_lds <= (uint64_t)kLdsMax)
-                p.cmode = kChainTable;
-            else if (fast_lds <= (uint64_t)kLdsMax)
-                p.cmode = kChainFast;
-        }
-        p.fast = p.cmode != kChainGeneral;
-        p.chain_lds = (uint32_t)(p.cmode == kChainTable  ? table_lds
-                                 : p.cmode == kChainFast ? fast_lds
-                                                         : pre + al(16 * E) + al(2ull * p.inv_stride) + tail);
-        p.n2p = (uint32_t)align_up(N * N, 8);
-        p.bm_words = (uint32_t)((binom(N, 4) + 31) / 32 + 1);
-        // k_h2_phase1: shared matrix + class table, then one bitmap + log per wave (2 waves when they fit)
-        const uint64_t p1_wave = al(4ull * p.bm_words) + 2 * al(4ull * kP1LogCap);
-        p.p1_waves = (pre + al(2ull * p.n2p) + kP1MaxWaves * p1_wave <= (uint64_t)kLdsMax && !test_env_is("TDA_P1_WAVES", "1"))
-                         ? kP1MaxWaves : 1;
-        p.p1_lds = (uint32_t)(pre + al(2ull * p.n2p) + p.p1_waves * p1_wave);
-        p.prep_lds = (uint32_t)(pre + al(8 * std::max<uint64_t>(2, next_pow2(E))));  // k_prep_edges' rank sort keys
-        if (p.chain_lds > (uint32_t)kLdsMax || p.prep_lds > (uint32_t)kLdsMax || p.p1_lds > (uint32_t)kLdsMax || p.dK == 0)
-            p.dense = false;
-    }
-    uint64_t maxp = 16;
-    for (int d = 1; d <= p.maxdim; ++d) maxp = std::max(maxp, p.pcap[d]);
-    p.sstride = 3 * maxp;
-
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        size_t r = o;
-        o = align_up(o + bytes, 256);
-        return r;
-    };
-    const size_t esz = p.dtype == TDA_F64 ? 8 : 4;
-    p.o_x = take(L * N * (p.is_dist ? N : (uint64_t)std::max<int64_t>(p.D, 1)) * esz);
-    {   // the distance kernels of this (N, D) and, for K slices, their partial Grams and norms
-        const DistSel ds = dist_select(N, p.D, p.dtype, p.is_dist != 0);
-        p.dsplit = ds.dsplit;
-        p.gram_layer = ds.gram_layer;
-        if (ds.partials()) {
-            const uint64_t sp = (uint64_t)ds.dsplit;
-            p.o_gpart = take(L * sp * N * N * 8);
-            p.o_npart = take(L * sp * N * 8);
-        }
-    }
-    p.o_dist = take(L * N * N * 4);
-    if (p.want64) p.o_d64 = take(L * N * N * 8);
-    p.memset_lo = o;
-    p.o_stats = take(L * sizeof(LayerStats));
-    p.o_mst = take(L * p.mst_words * 4);
-    // (TDA_PIV2_SPARSE=1 forces the sparse-clear bitmap at any size: the stale-bit tests at N = 300)
-    p.piv2_sparse = p.maxdim >= 2 && ((L * p.piv_words[2] * 4 >= (2ull << 30) && !test_env_is("TDA_PIV2_SPARSE", "0")) ||
-                                      test_env_is("TDA_PIV2_SPARSE", "1"));
-    for (int d = 1; d <= p.maxdim; ++d)
-        if (!(d == 2 && p.piv2_sparse)) p.o_piv[d] = take(L * p.piv_words[d] * 4);
-    p.o_rowmax = take(L * N * 4);
-    p.o_p1used = take(L * 8);
-    p.o_p1next = take(L * 4);
-    if (p.dense) {
-        p.o_res1 = take(L * p.piv_words[1] * 4);
-        p.o_necnt = take(L * 4);
-    }
-    p.memset_hi = o;
-    if (p.piv2_sparse) {
-        p.o_piv[2] = take(L * p.piv_words[2] * 4);
-        // one entry per apparent H2 pair (at most one per triangle); an overflow only costs a memset
-        p.clr_cap = std::min<uint64_t>(std::max<uint64_t>(p.ncand[2], 1), 1ull << 28);
-        p.o_clr2 = take(L * p.clr_cap * 8);
-    }
-    for (int d = 1; d <= p.maxdim; ++d) p.o_resid[d] = take(L * p.rcap[d] * 8);
-    p.o_tmp = take(L * 2 * p.max_rcap * 8);
-    if (p.maxdim >= 1) {
-        p.o_rmk = take(L * 2 * p.rmap_stride * 8);
-        p.o_rmv = take(L * 2 * p.rmap_stride * 4);
-        p.o_vlen = take(L * p.max_rcap * 4);
-        p.o_vpool = take(L * p.vpool_cap * 8);
-        p.o_voff = take(L * p.max_rcap * 8);
-        uint64_t wmax = p.lds_mode ? 8192 : p.wcap_g;
-        if (!p.big) p.o_wt = take(L * wmax * 8 * 2);  // slot scratch + compaction keys
-        // global working tables of the one-wave / serial radix-heap kernels (not needed when
-        // k_reduce_par takes H1 and there is no H2)
-        p.serial_tables = !p.lds_mode && !(p.par && (p.maxdim < 2 || p.par2));
-        if (p.serial_tables) {
-            p.o_wk = take(L * p.wcap_g * 8);       // key log
-            p.o_wl = take(L * p.wcap_g * 2 * 8);   // u64 index, 2 * wcap slots
-            p.o_wp = take(L * p.wcap_g / 4 * 4);   // bucket fill counters
-            if (p.big) p.o_bref = take(L * kNB * p.wcap_g * 4);  // radix-heap bucket references
-        }
-        if (p.wide) {
-            p.ecap = align_up(std::max<uint64_t>(binom(N, 2), 1), 32);
-            p.o_dsort = take(L * p.ecap * 8);
-            p.o_dtmp = take(L * p.ecap * 8);
-            p.o_dcode = take(L * N * N * 4);
-        }
-        if (p.par) {
-            // k_reduce_par: owner maps, final pivots, records, bucket chunks, requeue slots
-            const uint64_t prc = p.par2 ? std::max(p.rcap[1], p.rcap[2]) : p.rcap[1];
-            p.ostride = next_pow2(2 * prc + 16);
-            p.rec_cap = (2 * (uint64_t)L * prc + 4096) << scale;  // a capacity retry (scale) grows every pool
-            // bucket chunks: every workgroup keeps its peak bucket sizes (torus N=1024 needs ~2^26 keys
-            // in all, N=2048 ~2^28); records: raw copies of the paired columns.  HBM is 288 GB.
-            auto clampp = [](uint64_t x, int lo, int hi) { return std::min<uint64_t>(std::max<uint64_t>(next_pow2(x), 1ull << lo), 1ull << hi); };
-            // + chunks 0..3 of the kParLv buckets of every k_reduce_par workgroup
-            // above N = 1024 start at 4x (torus N=2048 overflows 2x: measured r02, 3 attempts per call).
-            // Per layer in the batch: every layer's long columns hold their bucket chunks at the same
-            // time, and zero-copy records keep theirs (r03: 32 torus1024 layers per call overflowed a
-            // per-call pool and fell back to the serial reducer)
-            const int big4 = N > 1024 ? 2 : 0;
-            // (at most 2^33 keys = 64 GiB of the 288 GiB; torus1024 x 32 layers draws ~2.5 G keys)
-            p.bpool_cap = std::min<uint64_t>(clampp(N * N * 128 * L, 24, 32) << (scale + big4), 1ull << 33) +
-                          (uint64_t)kParGrid * kParLv * 3840;
-            // H2 records as well: grid144 (32 layers) stores ~4.4 M keys of reduced H2 columns
-            p.rpool_cap = clampp(std::max<uint64_t>(N * N * 64 * std::min<uint64_t>(L, 8), p.par2 ? L * N * N * 8 : 0), 22, 29)
-                          << (scale + big4);
-            p.rq_cap = 1ull << (16 + scale);  // memset per launch: 0.5 MB at scale 0
-            p.o_pctl = take(sizeof(ParCtl));
-            p.o_pitem = take((L + 1) * 8);
-            p.o_pokey = take(L * p.ostride * 8);
-            p.o_poval = take(L * p.ostride * 8);
-            p.o_colpiv = take(L * prc * 8);
-            p.o_prec = take(p.rec_cap * 32);
-            p.o_prpool = take(p.rpool_cap * 8);
-            p.o_pbpool = take(p.bpool_cap * 8);
-            p.o_prq = take(p.rq_cap * 8);
-#if defined(TDA_PROFILE) || defined(TDA_PROF2)
-            p.o_pdbg = take((size_t)kParDbgCap * 32 + (size_t)kParDbgCap * kParP2Words * 8);
-#endif
-        }
-        if (p.dense) {
-            p.o_recs = take(L * binom(N, 2) * 16);
-            p.o_cls2 = take(L * (uint64_t)p.n2p * 2);
-            p.o_cls = take(L * binom(N, 2) * 4);
-            p.o_inv = take(L * (uint64_t)p.inv_stride * 2);
-            p.o_epos = take(L * binom(N, 2) * 4);
-            p.o_eM = take(L * binom(N, 2) * 8);
-            if (p.fast) {
-                p.o_inv32 = take(L * (uint64_t)p.inv_stride * 4);
-                p.o_rof = take(L * (uint64_t)p.tri_stride * 2);
-            }
-            if (p.cmode == kChainTable) p.o_cobt = take(L * (uint64_t)p.cob_stride * 2);
-            if (p.maxdim >= 2) {
-                p.o_p1k = take(L * p.rcap[2] * 8);
-                p.o_p1i = take(L * p.rcap[2] * 4);
-                p.o_p1x = take(L * p.rcap[2] * 4);
-                p.o_roff2 = take(L * p.rcap[2] * 8);
-                p.o_rlen2 = take(L * p.rcap[2] * 4);
-                p.o_rpool2 = take(L * p.vpool_cap * 8);
-            }
-        }
-    }
-    for (int d = 0; d <= p.maxdim; ++d) p.o_pairs[d] = take(L * p.pcap[d] * sizeof(Pair));
-    p.o_h0s = take(L * 2 * N * 8 + 64);
-    if (N > (uint64_t)kSmallN) {
-        p.o_bcomp = take(L * N * 4);
-        p.o_bcheap = take(L * N * 8);
-        p.o_bctl = take(L * sizeof(BorCtl));
-    }
-    p.o_fk = take(L * 2 * p.sstride * 8);
-    p.o_fv = take(L * 2 * p.sstride * 4);
-    p.o_pptr = take(4 * sizeof(void*));
-    p.o_pcap = take(4 * 8);
-    p.o_outoff = take(L * 4 * 8);
-    p.total = o;
-    return 0;
-}
 
 // ------------------------------------------------------------------ workspace
 struct Workspace {
@@ -1178,7 +772,7 @@ struct StreamSwap {
 void fill_graph_key(Call& c, GraphKey& gk) {
     const tda_rips_args& a = c.a;
     const Plan& p = c.p;
-    c.dist_mfma = c.input_kind == 0 && dist_use_mfma(p.D);
+    c.dist_mfma = p.dist.mfma;
     // column caps only with ripser's default threshold (the enclosing radius: no essential
     // H1 / H2 class); a finite user threshold can leave classes essential (k_reduce_par)
     // caps also off when H2 runs on the serial k_reduce_big after a parallel H1 (TDA_PAR2=0, or an H2
@@ -1202,8 +796,8 @@ void fill_graph_key(Call& c, GraphKey& gk) {
     gk.capf = c.capf;
     gk.variant = (p.dense ? 1 : 0) | (p.big ? 2 : 0) | (p.fast ? 4 : 0) | (p.lds_mode ? 8 : 0) | (p.cmode << 4) | (p.par ? 1 << 8 : 0) | (c.dist_mfma ? 1 << 9 : 0) |
                  (p.wide ? 1 << 10 : 0) | (p.want64 ? 1 << 11 : 0) | (p.par2 ? 1 << 12 : 0) | (p.piv2_sparse ? 1 << 13 : 0) |
-                 (p.gram_layer ? 1 << 14 : 0);
-    gk.dsplit = p.dsplit;
+                 (p.dist.gram_layer ? 1 << 14 : 0);
+    gk.dsplit = p.dist.dsplit;
     gk.thresh = a.thresh;
     gk.n_label_sets = c.nls;
     gk.sil_K = c.sil_K;  // baked into the k_silhouette launch (argument K and its LDS size)
@@ -1459,6 +1053,11 @@ struct HostProf {
     }
 };
 
+bool getenv_is(const char* name, const char* val) {
+    const char* m = getenv(name);
+    return m && !strcmp(m, val);
+}
+
 // One attempt of a call with the configuration `at`: plan, buffers, inputs, the launch sequence,
 // one synchronisation, then either the result (*out) or, in `step`, the attempt to run next.
 int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev, tda_rips_result** out, const Attempt& at,
@@ -1469,15 +1068,9 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
     Workspace& w = *get_ws(a.device, a.slot);
     std::unique_lock<std::mutex> guard(w.mu);  // released on return: a retry or a cap-miss re-run takes it again
     Call c(a, input_kind, host_or_dev, at, w);
-    Plan& p = c.p;
-    p.L = a.L;
-    p.N = a.N;
-    p.D = a.D;
-    p.maxdim = a.maxdim;
-    p.dtype = a.dtype;
-    p.is_dist = input_kind != 0;
-    p.want64 = input_kind == 0 && a.dtype == TDA_F64 && a.want_dist && (a.flags & TDA_FLAG_DIST64);
-    make_plan(p, at);
+    c.p = make_plan(a.L, a.N, a.D, a.maxdim, a.dtype, input_kind != 0,
+                    input_kind == 0 && a.dtype == TDA_F64 && a.want_dist && (a.flags & TDA_FLAG_DIST64), at);
+    const Plan& p = c.p;
     {
         std::lock_guard<std::mutex> rt_lock(g_capture_mu);  // buffers in place; a capture re-takes it
         if (int rc = prepare_buffers(c)) return rc;

@@ -10,30 +10,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rips_shapes.h"  // binom
+
 namespace tda {
 
 constexpr uint64_t kEmpty64 = 0xFFFFFFFFFFFFFFFFull;
-
-// ---------------------------------------------------------------- binomials
-// C(n, k) for k <= 5 without 64-bit division: 32-bit exact-division steps
-// (C(n,k) = C(n,k-1) * (n-k+1) / k, split so every quotient is exact) and one
-// 32x32->64 multiply at the end.  Valid for n < 65536 (checked on the host).
-__host__ __device__ __forceinline__ uint64_t binom(uint64_t n64, int k) {
-    const uint32_t n = (uint32_t)n64;
-    if (k == 0) return 1;
-    if (n < (uint32_t)k) return 0;
-    if (k == 1) return n;
-    const uint32_t c2 = (n & 1) ? n * ((n - 1) >> 1) : (n >> 1) * (n - 1);  // < 2^31 for n < 65536
-    if (k == 2) return c2;
-    // C3 = c2 * (n-2) / 3, c2 = 3q + r
-    const uint32_t q2 = c2 / 3u, r2 = c2 - 3u * q2;
-    const uint64_t c3 = (uint64_t)q2 * (n - 2) + (r2 * (n - 2)) / 3u;
-    if (k == 3) return c3;
-    const uint64_t c4 = (c3 >> 2) * (n - 3) + ((uint32_t)(c3 & 3) * (n - 3)) / 4u;
-    if (k == 4) return c4;
-    const uint64_t q4 = c4 / 5u, r4 = c4 - 5u * q4;
-    return q4 * (n - 4) + (r4 * (n - 4)) / 5u;
-}
 
 // largest v in [k-1, top] with C(v, k) <= idx.  The estimate is f32 hardware
 // math (sqrt / exp2-log2 cube root, within a vertex or two of the answer);

@@ -166,7 +166,7 @@ void wire_buffers(Call& c) {
     }
 }
 
-// ---- distances of (L, n, D) point clouds: the one kernel selection (DistSel, rips.hip) for every
+// ---- distances of (L, n, D) point clouds: the one kernel selection (DistSel, rips_plan.h) for every
 // entry that needs the sklearn-exact f32 matrix.  rowmax must be zeroed before; gpart / npart are
 // read only when sel.partials().  mark(name) closes a stage (the call's stage timer, or a no-op).
 struct DistLaunch {
@@ -235,11 +235,7 @@ int enqueue_distances(Call& c) {
             HIPC(hipMemcpyAsync(B + p.o_x, x, (size_t)L * n * p.D * c.esz, hipMemcpyHostToDevice, s));
             x = B + p.o_x;
         }
-        DistSel sel;
-        sel.mfma = c.dist_mfma;
-        sel.dsplit = p.dsplit;
-        sel.gram_layer = p.gram_layer;
-        const DistLaunch dl = {x, p.dtype, n, p.D, L, sel, dist, rowmax, (double*)(B + p.o_gpart), (double*)(B + p.o_npart),
+        const DistLaunch dl = {x, p.dtype, n, p.D, L, p.dist, dist, rowmax, (double*)(B + p.o_gpart), (double*)(B + p.o_npart),
                                p.want64 ? (double*)(B + p.o_d64) : nullptr};
         if (int rc = launch_point_distances(s, dl, [&](const char* name) { return c.tm.mark(name); })) return rc;
     } else {
@@ -263,7 +259,7 @@ int enqueue_distances(Call& c) {
         hipLaunchKernelGGL(k_rowmax, dim3((n + 3) / 4, L), dim3(256), 0, s, dist, n, rowmax);
     }
     HIPC(hipGetLastError());
-    MARK(c.input_kind != 0 ? "k_square_dist" : c.dist_mfma ? ((p.dsplit > 1 || p.gram_layer) && p.dtype == TDA_F32 ? "k_rowmax" : "k_distance_mfma") : "k_distance");
+    MARK(c.input_kind != 0 ? "k_square_dist" : c.dist_mfma ? (p.dist.partials() && p.dtype == TDA_F32 ? "k_rowmax" : "k_distance_mfma") : "k_distance");
     return 0;
 }
 

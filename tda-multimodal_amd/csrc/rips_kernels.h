@@ -22,10 +22,7 @@
 namespace tda {
 
 // ------------------------------------------------------------------ layout
-struct Pair {
-    float birth, death;
-    int64_t birth_idx, death_idx;
-};
+// (Pair and LayerStats: rips_shapes.h)
 // typed (non-FLAT) store of one pair to HBM
 __device__ __forceinline__ void store_pair(Pair* P, uint64_t i, float b, float d, int64_t bi, int64_t di) {
     uint64_t* q = (uint64_t*)(P + i);
@@ -33,23 +30,6 @@ __device__ __forceinline__ void store_pair(Pair* P, uint64_t i, float b, float d
     st_glb(q, 1, (uint64_t)bi);
     st_glb(q, 2, (uint64_t)di);
 }
-
-struct LayerStats {  // zeroed every call; copied to the host result
-    float thresh;
-    int32_t err;  // bit flags, see ERR_*
-    int64_t num_edges;
-    int64_t count[4];      // emitted pairs per dim
-    uint64_t checksum[4];  // sum of pair_hash over all pairs
-    int64_t all_pairs[4];
-    int64_t n_columns[4];
-    int64_t n_residual[4];
-    int64_t n_adds[4];     // column additions in the serial reduction
-    int64_t nskip[4];      // residual columns cleared by the serial reduction (host: n_residual - nskip)
-    uint64_t rmask[4];     // residual pivot map mask used by the dim's reducer (HBM map consumers)
-    int64_t ntri;          // N <= 64: triangles <= thresh (k_prep_tables)
-    int64_t n_clr2;        // sparse-cleared H2 pivot bitmap: words k_apparent<2> listed for the end-of-call clear
-    uint64_t prof[5][8];   // -DTDA_PROFILE builds: cycle counters (per dim; [3]: k_h0_wave, [4]: k_prep_layer)
-};
 
 struct DimBufs {              // per reduction dim d (columns = d-simplices)
     const uint32_t* cleared;  // bitmap over d-simplices (per layer stride)
@@ -175,10 +155,7 @@ __global__ __launch_bounds__(256) void k_distance(const T* __restrict__ X, int n
 // 2.7e-6 at D = 96 .. 1050, exactly 0 at D = 4096; k_gram_layer and k_distance, whose norms run
 // in the products' k order, return exactly 0).  The bound is sqrt(E) of tests/dist_ref.py;
 // tests/test_distance_paths.py prints the value per path.
-#ifndef TDA_DM_KC  // build-time A/B knob (tools/): K chunk of k_distance_mfma
-#define TDA_DM_KC 32
-#endif
-constexpr int kDmT = 64, kDmKC = TDA_DM_KC, kDmS = kDmKC + 2;
+constexpr int kDmS = kDmKC + 2;  // (kDmT, kDmKC: rips_shapes.h)
 typedef double dm_d4 __attribute__((ext_vector_type(4)));
 
 // METRIC 1: cosine distance instead (UMAP input, umap.distances.cosine:
@@ -409,7 +386,7 @@ __global__ __launch_bounds__(256) void k_distance_mfma(const T* __restrict__ X, 
 // N = 144) and the MFMA work is spread evenly over the waves.  Partial Gram
 // entries (i < j) and row norms per slice go to k_distance_combine, the same
 // fixed-order combine as the tiled split.  f32 input, Euclidean.
-constexpr int kGlMaxNB = 9, kGlMaxN = 16 * kGlMaxNB, kGlMB = (kGlMaxNB * (kGlMaxNB + 1) / 2 + 3) / 4;
+constexpr int kGlMB = (kGlMaxNB * (kGlMaxNB + 1) / 2 + 3) / 4;  // (kGlMaxNB, kGlMaxN: rips_shapes.h)
 __global__ __launch_bounds__(256) void k_gram_layer(const float* __restrict__ X, int n, int D, double* __restrict__ gpart,
                                                     double* __restrict__ npart) {
     __shared__ float xs[2][kGlMaxN][kDmS];
@@ -747,11 +724,6 @@ __device__ void block_sort(uint64_t* keys, uint32_t* vals, uint64_t n, uint64_t*
 // new forest edges, pointer jumping flattens the components).  The forest is
 // the unique minimum spanning forest of the total order, i.e. Kruskal's;
 // k_h0<0, false> then sorts it and runs the elder rule.
-struct BorCtl {
-    unsigned long long nmst;  // forest edges found
-    uint32_t done, pad;
-};
-
 __global__ __launch_bounds__(256) void k_bor_init(const uint32_t* __restrict__ rowmax, int n, float user_thresh,
                                                   LayerStats* __restrict__ stats, int32_t* __restrict__ comp,
                                                   uint64_t* __restrict__ cheap, BorCtl* __restrict__ ctl) {
@@ -868,7 +840,6 @@ __global__ __launch_bounds__(1024) void k_bor_hook(int n, int32_t* __restrict__ 
     for (int v = t; v < n; v += T) cg[v] = hook[cs[v]];
 }
 
-constexpr int kH0WaveMaxN = 190;  // 4 n^2 B of LDS staging
 constexpr int kH0WaveQ = (kH0WaveMaxN + 63) / 64;
 constexpr int kH0BorWQ = 16;  // Borůvka path: one-wave elder rule with register labels up to N = 1024
 template <int WQ, bool LROWS, bool BOR = false>

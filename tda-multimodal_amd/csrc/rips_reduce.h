@@ -302,17 +302,6 @@ struct SmallBufs {
 constexpr uint32_t kP1Overflow = 1u << 31;  // phase-1 column outgrew its LDS table
 constexpr uint32_t kP1Cleared = 1u << 30;   // phase 2: the column is an H1 death (prefetched flag)
 
-struct Reduce2Cfg {  // per-dim LDS carve, decided on the host
-    uint32_t wcap, rmap_lds_cap;  // rmap_lds_cap = 0 -> global map
-    int piv_lds;
-};
-struct ReduceAllCfg {
-    Reduce2Cfg dim[3];
-    uint64_t step_limit;  // pivots per column before giving up (exit guarantee)
-    int dist_lds;
-    uint32_t bytes;  // dynamic LDS of the launch
-};
-
 // residual pivot map of one dim: open addressing, key = row payload lo32.
 // lds: the table lives in LDS (typed accesses), else in HBM.
 struct PivMap {

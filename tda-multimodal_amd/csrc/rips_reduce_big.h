@@ -20,7 +20,6 @@ namespace tda {
 
 constexpr int kBigT = 1024;    // threads per layer
 constexpr int kBigW = kBigT / 64;
-constexpr int kNB = 33;        // radix buckets (f32 diameter bits)
 
 struct BigBufs {
     uint64_t* log;       // [L][cap] keys (| kDead)

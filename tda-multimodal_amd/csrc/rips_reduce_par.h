@@ -81,17 +81,6 @@ constexpr uint64_t kParEss = kEmpty64;        // colpiv: essential (zero column)
 constexpr uint64_t kParSkip = kEmpty64 - 1;   // colpiv: cleared column (H0 death)
 constexpr uint32_t kParSpin = 1u << 22;       // polls before a wait on another workgroup is declared hung
 
-struct ParCtl {  // zeroed by k_par_init
-    unsigned long long next;     // next fresh item
-    unsigned long long rq_head, rq_tail;
-    unsigned long long bpool_used, rpool_used, rec_used;
-    unsigned long long abort;
-    unsigned long long err;      // first error code (diagnostics)
-    unsigned long long total;    // items over all layers
-    unsigned long long evictions;
-    unsigned long long pad[6];
-};
-
 struct ParBufs {
     ParCtl* ctl;
     uint64_t* item_base;  // [L + 1] prefix of per-layer residual counts
@@ -111,8 +100,6 @@ struct ParBufs {
     float capf;           // column caps: keys above birth + capf * thresh are dropped (0 = off); see k_reduce_par
     uint64_t* dbg;        // -DTDA_PROFILE: [kParDbgCap][4] long-column timeline (layer << 40 | column, start, end, steps)
 };
-constexpr uint32_t kParDbgCap = 4096;
-constexpr uint32_t kParP2Words = 12;       // -DTDA_PROF2 record: layer << 40 | column, wave, steps, 8 phase cycle sums, spare
 constexpr uint64_t kParP2MinSteps = 1000;
 constexpr uint64_t kParDbgMinSteps = 256;  // columns with at least this many steps are logged
 
@@ -142,7 +129,7 @@ __device__ __forceinline__ void drain_vm() { asm volatile("s_waitcnt vmcnt(0)" :
 // edge code) shared level 0, which the front had to hold at once: torus1024's
 // H2 columns exceeded it and fell back to the serial reducer.  Level 0 now
 // means equal keys, which cancel in the front.
-constexpr int kParLv = 65;
+// (kParLv levels: rips_shapes.h)
 __device__ __forceinline__ uint32_t par_bucket(uint64_t key, uint64_t last) {
     const uint64_t x = key ^ last;
     return x ? 64u - (uint32_t)__builtin_clzll(x) : 0u;

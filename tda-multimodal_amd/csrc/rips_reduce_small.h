@@ -41,11 +41,9 @@
 
 namespace tda {
 
-constexpr int kDenseMaxN = 64;
 constexpr int kChainT = 1024;             // threads per k_h1_chain block (staging; the chain is wave 0)
 constexpr int kP1Grid = 96;               // k_h2_phase1 blocks per layer at most (one wave each, strided columns; rips.hip sizes it by L)
 constexpr uint32_t kP1WCap = 512;         // phase-1 toggle-set capacity
-constexpr int kChainMaxCols = 512;        // non-cleared H1 residual columns / stored R_j per layer
 constexpr int kMaxK = 21;                 // bitmap words per lane: ceil(C(64,3) / 32 / 64)
 
 __device__ __forceinline__ uint32_t edge_id(int a, int b) { return a > b ? c2u(a) + b : c2u(b) + a; }
@@ -135,8 +133,6 @@ constexpr int kPrepEdges = 256;  // edges per k_prep_edges mask block (16 per wa
 constexpr uint32_t kNoRank = 0xFFFFFFFFu;
 // inv16[rank] = edge | flags (edge < 2048 for N <= 64)
 constexpr uint32_t kInvEdge = 0x7FFu, kInvFirst = 1u << 11, kInvTie = 1u << 12, kInvRes = 1u << 13;
-// k_h1_chain variants (template MODE)
-constexpr int kChainGeneral = 0, kChainFast = 1, kChainTable = 2;
 
 // Grid (L, nb + 1), nb = ceil(E / kPrepEdges), kPrepT threads.  Blocks
 // y >= 1: the block masks M_e of their kPrepEdges edges (wave per edge, lane
@@ -975,9 +971,6 @@ __global__ __launch_bounds__(kChainT) void k_h1_chain(const float* __restrict__ 
 #endif
     h1_chain_wave<K, MODE>(c);
 }
-// bitmap words per lane supported by k_h1_chain instantiations (FAST / TABLE: up to 12)
-constexpr int kChainKs[] = {1, 2, 3, 4, 6, 9, 12, 16, 21};
-constexpr int kChainFastMaxK = 12;
 
 // ---------------------------------------------------------------- H2 phase 1
 // One wave per block; block (l, g) takes the layer's residual H2 columns
@@ -994,7 +987,6 @@ constexpr int kChainFastMaxK = 12;
 //     get_zero_apparent_facet], so this equals k_apparent's bitmap).
 // Results go out in the u64 key format of the serial phase 2.
 // LDS: [16][D][cls2][bitmap][log][log vertices].
-constexpr uint32_t kP1LogCap = 1024;
 // Phase-1 additions per column before handing the column to the serial phase
 // 2.  The long phase-1 chains are H2 columns that turn out to be H1 deaths
 // (cleared once the H1 chain pairs them); the kept columns of the 32-layer
@@ -1010,7 +1002,6 @@ __device__ __forceinline__ uint32_t c2s(uint32_t x) { return x < 2 ? 0u : x * (x
 // independent waves: the layer's matrix and class table are staged once per
 // block and shared; each wave has its own bitmap and log and takes its own
 // columns (virtual one-wave block blockIdx.y * waves + wave).
-constexpr int kP1MaxWaves = 2;
 __global__ __launch_bounds__(64 * kP1MaxWaves) void k_h2_phase1(const float* __restrict__ dist, int n, LayerStats* __restrict__ stats,
                                                                 DimBufs b, SmallBufs sb, const uint16_t* __restrict__ cls2g, uint32_t n2p,
                                                                 uint32_t bm_words, const uint32_t* __restrict__ res1g, uint32_t res1_words,

@@ -1,4 +1,4 @@
-"""Every launch path of the distance stage (dist_select, csrc/rips.hip) against
+"""Every launch path of the distance stage (dist_select, csrc/rips_plan.h) against
 a longdouble truth with a derived bound (tests/dist_ref.py), the oracle, the
 exact integer grid, and persistence on the matrix actually returned.
 

@@ -1,0 +1,255 @@
+"""The host plan of a persistence call (csrc/rips_plan.h, make_plan) on the CPU.
+
+tests/rips_plan_main.cpp includes only rips_plan.h; it is compiled with g++ under the address and
+undefined-behaviour sanitizers and run as a program of its own, once per environment.  Three checks:
+
+* the pin: the plans of PIN_CASES reproduce tests/golden/rips_plan.txt byte for byte.  The file was
+  recorded by this program when make_plan had just been moved out of rips.hip, bodies untouched.
+  To record it again: python tests/test_rips_plan_cpu.py | <the program> > tests/golden/rips_plan.txt
+* invariants of every plan (alignment, regions that do not overlap, LDS sizes, reducer selection),
+  from sizes restated here, for the pin's cases and for random shapes;
+* a test knob forces the field it is named for at the shapes where the GPU tests set it, and
+  changes nothing without TDA_TEST_OVERRIDES=1.
+"""
+import math
+import os
+import random
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "tda-multimodal_amd", "csrc")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "rips_plan.txt")
+
+F32, F64 = 0, 1
+K_LDS_MAX, K_DENSE_MAX_N = 160 * 1024, 64
+CHAIN_KS = (1, 2, 3, 4, 6, 9, 12, 16, 21)
+SIZEOF = {"Pair": 24, "LayerStats": 608, "BorCtl": 16, "ParCtl": 128}
+NS = (1, 2, 3, 8, 24, 64, 65, 144, 145, 190, 191, 256, 257, 568, 569, 1024, 1025, 2048)
+
+
+def case(L, N, D=3, maxdim=1, dtype=F32, is_dist=0, want64=0, force_global=0, scale=0, force_big=0, no_par=0):
+    return (L, N, D, maxdim, dtype, is_dist, want64, force_global, scale, force_big, no_par)
+
+
+def pin_cases():
+    """The cross product of the pin, thinned: every N at every maxdim for L = 1 and 32; the other axes at a few N each."""
+    cs = [case(L, n, maxdim=md) for L in (1, 32) for md in (0, 1, 2) for n in NS]
+    cs += [case(L, n, D, 1, dt) for L, n in ((1, 8), (32, 144), (1, 145), (32, 1024)) for D in (32, 4096) for dt in (F32, F64)]
+    cs += [case(1, n, n, 2, dt, is_dist=1) for n in (8, 65, 257) for dt in (F32, F64)]
+    cs += [case(L, n, D, 1, F64, want64=1) for L, n, D in ((1, 24, 3), (32, 24, 32), (1, 145, 3), (32, 145, 4096))]
+    cs += [case(L, n, maxdim=2, scale=s) for L, n in ((32, 64), (1, 256), (1, 1025)) for s in (1, 2, 3, 4)]
+    cs += [case(L, n, maxdim=md, force_global=1) for L, n in ((32, 8), (1, 64)) for md in (1, 2)]
+    cs += [case(1, n, maxdim=md, force_global=1, force_big=1, scale=s) for n, s in ((64, 0), (65, 1), (256, 2)) for md in (1, 2)]
+    cs += [case(L, n, maxdim=2, no_par=k) for L, n in ((32, 65), (1, 257), (1, 569)) for k in (1, 2)]
+    cs += [case(1, 2048, maxdim=2, scale=4, no_par=1)]
+    return cs
+
+
+@pytest.fixture(scope="module")
+def exe(tmp_path_factory):
+    out = str(tmp_path_factory.mktemp("rips_plan") / "rips_plan")
+    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I" + CSRC, "-o", out, os.path.join(ROOT, "tests", "rips_plan_main.cpp")], check=True)
+    return out
+
+
+def run_text(exe, cases, knobs=None, gate=True):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("TDA_")}
+    env.update(knobs or {})
+    if gate:
+        env["TDA_TEST_OVERRIDES"] = "1"
+    text = "".join(" ".join(map(str, c)) + "\n" for c in cases)
+    return subprocess.run([exe], input=text, capture_output=True, text=True, check=True, env=env).stdout
+
+
+def parse(text, n_cases):
+    """-> (sizes of the first line, one dict per case: name -> int or list of ints)"""
+    blocks = text.split("\ncase ")
+    head = dict((k, int(v)) for k, v in (t.split("=") for t in blocks[0].split()[1:]))
+    plans = []
+    for b in blocks[1:]:
+        p = {}
+        for tok in b.split("\n", 1)[1].split():
+            if "=" in tok:
+                k, v = tok.split("=")
+                p[k] = [int(x) for x in v.split(",")] if "," in v else int(v)
+        plans.append(p)
+    assert len(plans) == n_cases
+    return head, plans
+
+
+def plans_of(exe, cases, knobs=None, gate=True):
+    return parse(run_text(exe, cases, knobs, gate), len(cases))[1]
+
+
+def test_pin(exe):
+    got = run_text(exe, pin_cases())
+    with open(GOLDEN) as f:
+        assert got == f.read()
+    assert os.path.getsize(GOLDEN) <= max(os.path.getsize(os.path.join(os.path.dirname(GOLDEN), f)) for f in os.listdir(os.path.dirname(GOLDEN))
+                                          if f != "rips_plan.txt")
+
+
+def test_pin_holds_every_boundary():
+    cs = pin_cases()
+    for md in (0, 1, 2):
+        assert {c[1] for c in cs if c[3] == md} >= set(NS)
+    assert {c[0] for c in cs} == {1, 32} and {c[2] for c in cs} >= {3, 32, 4096} and {c[4] for c in cs} == {F32, F64}
+    assert {c[8] for c in cs} == {0, 1, 2, 3, 4} and {c[10] for c in cs} == {0, 1, 2}
+    assert any(c[5] for c in cs) and any(c[6] for c in cs) and any(c[7] for c in cs) and any(c[9] for c in cs)
+    assert case(32, 2048, maxdim=2) in cs  # the sparse pivot bitmap, far above 2 GB
+
+
+def region_sizes(c, p):
+    """Bytes of the regions whose size follows from the printed capacities (restated, not read from make_plan)."""
+    L, N, D, maxdim, dtype, is_dist = c[:6]
+    S = SIZEOF
+    sz = {
+        "o_x": L * N * (N if is_dist else max(D, 1)) * (8 if dtype == F64 else 4),
+        "o_gpart": L * p["dist.dsplit"] * N * N * 8, "o_npart": L * p["dist.dsplit"] * N * 8,
+        "o_dist": L * N * N * 4, "o_d64": L * N * N * 8, "o_rowmax": L * N * 4,
+        "o_stats": L * S["LayerStats"], "o_mst": L * p["mst_words"] * 4,
+        "o_p1used": L * 8, "o_p1next": L * 4, "o_res1": L * p["piv_words"][1] * 4, "o_necnt": L * 4, "o_clr2": L * p["clr_cap"] * 8,
+        "o_tmp": L * 2 * p["max_rcap"] * 8, "o_rmk": L * 2 * p["rmap_stride"] * 8, "o_rmv": L * 2 * p["rmap_stride"] * 4,
+        "o_vlen": L * p["max_rcap"] * 4, "o_vpool": L * p["vpool_cap"] * 8, "o_voff": L * p["max_rcap"] * 8,
+        "o_h0s": L * 2 * N * 8 + 64, "o_bcomp": L * N * 4, "o_bcheap": L * N * 8, "o_bctl": L * S["BorCtl"],
+        "o_fk": L * 2 * p["sstride"] * 8, "o_fv": L * 2 * p["sstride"] * 4, "o_pptr": 32, "o_pcap": 32, "o_outoff": L * 32,
+        "o_pctl": S["ParCtl"], "o_pitem": (L + 1) * 8, "o_pokey": L * p["ostride"] * 8, "o_poval": L * p["ostride"] * 8,
+        "o_prec": p["rec_cap"] * 32, "o_prpool": p["rpool_cap"] * 8, "o_pbpool": p["bpool_cap"] * 8, "o_prq": p["rq_cap"] * 8,
+        "o_dsort": L * p["ecap"] * 8, "o_dtmp": L * p["ecap"] * 8, "o_dcode": L * N * N * 4,
+    }
+    for d in range(1, maxdim + 1):
+        sz["o_piv%d" % d] = L * p["piv_words"][d] * 4
+        sz["o_resid%d" % d] = L * p["rcap"][d] * 8
+    for d in range(maxdim + 1):
+        sz["o_pairs%d" % d] = L * p["pcap"][d] * S["Pair"]
+    return sz
+
+
+def check_invariants(c, p, knobs_set=False):
+    L, N, D, maxdim = c[:4]
+    offs = {}
+    for k, v in p.items():
+        if k.startswith("o_"):
+            offs.update({"%s%d" % (k, i): x for i, x in enumerate(v)} if isinstance(v, list) else {k: v})
+    assert p["o_x"] == 0
+    live = {k: v for k, v in offs.items() if v != 0 or k == "o_x"}
+    for k, v in live.items():
+        assert v % 256 == 0, (c, k)
+    sz = region_sizes(c, p)
+    for k in ["o_dist", "o_stats", "o_mst"] + ["o_%s%d" % (n, d) for n in ("piv", "resid", "pairs") for d in range(1, maxdim + 1)] + ["o_pairs0"]:
+        assert k in live and k in sz, (c, k)
+    order = sorted(live.items(), key=lambda kv: kv[1])
+    for (k, v), (k2, v2) in zip(order, order[1:] + [("total", p["total"])]):
+        assert v + sz.get(k, 1) <= v2, (c, k, k2)
+    # the memset range
+    assert p["memset_lo"] <= p["o_stats"] < p["memset_hi"], c
+    for d in range(1, maxdim + 1):
+        if d == 2 and p["piv2_sparse"]:
+            assert p["o_piv"][2] >= p["memset_hi"], c
+        else:
+            assert p["memset_lo"] <= p["o_piv"][d] and p["o_piv"][d] + sz["o_piv%d" % d] <= p["memset_hi"], c
+    # LDS
+    for k in ("chain_lds", "p1_lds", "prep_lds", "rcfg.bytes"):
+        assert p[k] <= K_LDS_MAX, (c, k)
+    if p["dense"]:
+        assert 3 <= N <= K_DENSE_MAX_N and p["dK"] in CHAIN_KS and 64 * 32 * p["dK"] >= math.comb(N, 3), c
+    # reducer selection
+    assert not p["par2"] or p["par"], c
+    assert not p["par"] or p["big"], c
+    assert not p["big"] or not p["lds_mode"], c
+    if not knobs_set:
+        assert bool(p["wide"]) == (bool(p["big"]) and maxdim >= 2 and N > 568), c
+
+
+def test_struct_sizes_and_limits(exe):
+    head, _ = parse(run_text(exe, []), 0)
+    assert head == dict(SIZEOF, kLdsMax=K_LDS_MAX, kDenseMaxN=K_DENSE_MAX_N)
+
+
+def test_invariants_of_the_pin(exe):
+    cs = pin_cases()
+    for c, p in zip(cs, plans_of(exe, cs)):
+        check_invariants(c, p)
+
+
+def random_cases(n, seed):
+    rng = random.Random(seed)
+    cs = []
+    for _ in range(n):
+        N = rng.choice([rng.randint(1, 70), rng.randint(1, 300), rng.randint(1, 2048)])
+        dt = rng.choice((F32, F64))
+        is_dist = rng.random() < 0.2
+        cs.append(case(rng.randint(1, 64), N, N if is_dist else rng.choice((1, 3, 31, 32, 100, 1050, 4096)), rng.randint(0, 2), dt, int(is_dist),
+                       int(not is_dist and dt == F64 and rng.random() < 0.3), int(rng.random() < 0.2), rng.randint(0, 4), int(rng.random() < 0.2),
+                       rng.randint(0, 2)))
+    return cs
+
+
+def test_invariants_of_random_shapes(exe):
+    cs = random_cases(400, 7)
+    for c, p in zip(cs, plans_of(exe, cs)):
+        check_invariants(c, p)
+
+
+def test_dist_sel_does_not_depend_on_L(exe):
+    base = [case(1, n, D, 1, dt) for n in (17, 40, 144, 145, 200, 1024) for D in (3, 32, 260, 1050, 4096) for dt in (F32, F64)]
+    ref = plans_of(exe, base)
+    for L in (2, 32, 64):
+        for a, b in zip(ref, plans_of(exe, [(L,) + c[1:] for c in base])):
+            assert [a[k] for k in ("dist.mfma", "dist.dsplit", "dist.gram_layer")] == [b[k] for k in ("dist.mfma", "dist.dsplit", "dist.gram_layer")]
+
+
+# (knobs, [(L, N, D, maxdim, dtype)] where tests/test_gpu_parity.py or tests/test_distance_paths.py set them -- or, for the
+# three knobs no GPU test sets (TDA_PAR=0, TDA_P1_WAVES=1, TDA_PIV2_SPARSE=0), a shape of the neighbouring test --, the fields forced)
+SWEEP48, GRID144_8, GRID144_6, TORUS256, TORUS300, ADV324 = (32, 48, 3, 2, F32), (8, 144, 3, 2, F32), (6, 144, 3, 2, F32), (1, 256, 3, 2, F32), \
+    (1, 300, 3, 2, F32), (1, 324, 3, 2, F32)
+FORCED = [
+    ({"TDA_REDUCE": "wave"}, [GRID144_8, TORUS256], {"big": 0, "par": 0, "lds_mode": 0}),
+    # (big = 1 is all TDA_REDUCE=big forces: par and par2 stay 1 at these shapes, as without the knob, so H1 and H2 run on
+    # k_reduce_par and the serial radix heap itself is reached only with TDA_PAR=0 / TDA_PAR2=0 or after an abort)
+    ({"TDA_REDUCE": "big"}, [GRID144_8, TORUS256], {"big": 1}),
+    ({"TDA_REDUCE": "par", "TDA_PAR_STRICT": "1"}, [GRID144_6, TORUS256, ADV324], {"par": 1, "par2": 1}),
+    ({"TDA_PAR": "0"}, [TORUS300, GRID144_8], {"par": 0, "par2": 0, "serial_tables": 1}),
+    ({"TDA_PAR2": "0"}, [(1, 600, 3, 2, F32), TORUS300], {"par": 1, "par2": 0, "serial_tables": 1}),
+    ({"TDA_PAR2": "1"}, [(1, 500, 3, 2, F32), TORUS300], {"par": 1, "par2": 1}),
+    ({"TDA_H2_WIDE": "1", "TDA_PAR2": "1"}, [TORUS300], {"wide": 1, "par2": 1}),
+    ({"TDA_H2_WIDE": "1", "TDA_PAR2": "0"}, [TORUS300], {"wide": 1, "par2": 0}),
+    ({"TDA_H2_WIDE": "0"}, [TORUS300], {"wide": 0}),
+    ({"TDA_CHAIN": "general"}, [SWEEP48, (3, 48, 2, 2, F32), (3, 48, 3, 2, F32)], {"dense": 1, "cmode": 0, "fast": 0}),
+    ({"TDA_CHAIN": "fast"}, [SWEEP48, (3, 48, 2, 2, F32), (3, 48, 3, 2, F32)], {"dense": 1, "cmode": 1, "fast": 1}),
+    ({"TDA_CHAIN": "auto"}, [SWEEP48], {"dense": 1, "cmode": 2, "fast": 1}),
+    ({"TDA_P1_WAVES": "1"}, [SWEEP48], {"dense": 1, "p1_waves": 1}),
+    ({"TDA_PIV2_SPARSE": "1"}, [TORUS300], {"piv2_sparse": 1}),
+    ({"TDA_PIV2_SPARSE": "0"}, [(1, 2048, 3, 2, F32)], {"piv2_sparse": 0}),
+    ({"TDA_DIST": "scalar"}, [(3, 145, 257, 1, F32), (3, 145, 257, 1, F64), (2, 63, 64, 2, F32), (2, 130, 37, 2, F64)], {"dist.mfma": 0, "dist.dsplit": 1, "dist.gram_layer": 0}),
+    ({"TDA_DIST": "mfma"}, [(2, 200, 3, 2, F32), (2, 200, 3, 2, F64), (2, 5, 33, 2, F32)], {"dist.mfma": 1}),
+    ({"TDA_DIST": "tiles"}, [(3, 63, 100, 1, F32), (3, 40, 1050, 1, F32)], {"dist.mfma": 1, "dist.gram_layer": 0}),
+    ({"TDA_DIST": "tiles", "TDA_DIST_SPLIT": "3"}, [(3, 130, 224, 1, F32)], {"dist.mfma": 1, "dist.dsplit": 3, "dist.gram_layer": 0}),
+    ({"TDA_DIST_SPLIT": "5"}, [(3, 40, 1050, 1, F32)], {"dist.mfma": 1, "dist.dsplit": 5, "dist.gram_layer": 1}),
+    ({"TDA_DIST_SPLIT": "7"}, [(3, 65, 260, 1, F64)], {"dist.mfma": 1, "dist.dsplit": 7, "dist.gram_layer": 0}),
+]
+# what the same shapes get with no knob: the forced value is another one wherever the knob is not the default's name
+DEFAULTS = {"p1_waves": 2, "cmode": 2}
+
+
+@pytest.mark.parametrize("knobs,shapes,want", FORCED, ids=lambda x: ",".join("%s=%s" % kv for kv in x.items()) if isinstance(x, dict) and any(
+    k.startswith("TDA_") for k in x) else None)
+def test_forced_variant_names_what_it_runs(exe, knobs, shapes, want):
+    cs = [case(*s) for s in shapes]
+    plain = plans_of(exe, cs)
+    for c, p, q in zip(cs, plans_of(exe, cs, knobs), plain):
+        for k, v in want.items():
+            assert p[k] == v, (knobs, c, k)
+        check_invariants(c, p, knobs_set=True)
+        for k, v in DEFAULTS.items():
+            if k in want and q["dense"]:
+                assert q[k] == v, (c, k)
+    assert plans_of(exe, cs, knobs, gate=False) == plain  # no gate: the knobs change nothing
+
+
+if __name__ == "__main__":
+    sys.stdout.write("".join(" ".join(map(str, c)) + "\n" for c in pin_cases()))
