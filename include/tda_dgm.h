@@ -403,6 +403,43 @@ typedef struct tda_hk_result {
 int tda_heat_kernel(const tda_hk_args *args, tda_hk_result **out);
 void tda_hk_free(tda_hk_result *r);
 
+/* The Frechet mean (2-Wasserstein barycenter; Turner, Mileyko, Mukherjee, Harer 2014) of S diagrams:
+ * the argument struct and the limits of an entry that is NOT in the library yet
+ * (DESIGN.md section 7).  What exists is its host plan, csrc/fm_plan.h (the argument checks in the
+ * order below, the finite points, the start, the launch class of a step), and the CPU restatement of
+ * the definition, tests/fm_ref.py.  Neither a result struct nor a function is declared here until
+ * the device side ships.
+ *     F(Y)       = (1 / S) sum_j W2^2(Y, X_j)
+ *     W2^2(Y, X) = min over partial matchings of the sum of the costs paid
+ *     c(p, q)    = db db + dd dd,   c(p) = (pers pers) 0.5      each operation rounded on its own
+ * A step matches Y against every X_j, replaces every y that has k >= 1 partners (taken in increasing
+ * j, sums left to right from the first partner) by ((k mb + (S - k) w) / S, (k md + (S - k) w) / S)
+ * with mb = sb / k, md = sd / k, w = (mb + md) 0.5, drops a y without a partner, and appends, for j
+ * and within j for i increasing, that update (k = 1) of every point of X_j no y took.  The iteration
+ * ends when a step returns its input bit for bit, or after max_iter steps.
+ * The plan's checks, in this order: args NULL, S < 0, offsets NULL, reserved != 0, an unknown bit of
+ * flags, max_iter < 1 (TDA_E_INVALID), max_iter > TDA_FM_MAX_ITER (TDA_E_UNSUPPORTED), S < 1
+ * (TDA_E_INVALID), S > TDA_FM_MAX_DIAGRAMS (TDA_E_UNSUPPORTED), the layout of offsets and points,
+ * init_index outside {-1} u [0, S), init_n < 0 or init_points NULL (TDA_E_INVALID), then a diagram
+ * or a start with more than TDA_FM_MAX_POINTS finite points (TDA_E_UNSUPPORTED). */
+#define TDA_FM_MAX_POINTS 512    /* finite points of one diagram and of Y at every step (= TDA_WS_MAX_POINTS) */
+#define TDA_FM_MAX_DIAGRAMS 4096 /* S at most                                                                 */
+#define TDA_FM_MAX_ITER 1024     /* max_iter at most                                                          */
+#define TDA_FM_WANT_MATCHING 1
+
+typedef struct tda_fm_args {
+    const double *points;      /* host (total, 2) f64 (birth, death); non-finite rows are skipped     */
+    const int64_t *offsets;    /* host [S + 1] non-decreasing row boundaries, offsets[0] = 0          */
+    int64_t S;                 /* diagrams, 1 .. TDA_FM_MAX_DIAGRAMS                                  */
+    int64_t init_index;        /* Y_0 = the finite points of diagram init_index, or -1: init_points   */
+    const double *init_points; /* host (init_n, 2) f64: the caller's start (init_index == -1)         */
+    int64_t init_n;            /* its rows, >= 0; non-finite rows are skipped                         */
+    int32_t max_iter;          /* steps at most, 1 .. TDA_FM_MAX_ITER                                 */
+    int32_t device;            /* HIP device ordinal                                                  */
+    int32_t flags;             /* 0 or TDA_FM_WANT_MATCHING                                           */
+    int32_t reserved;          /* must be 0                                                           */
+} tda_fm_args;
+
 #ifdef __cplusplus
 }
 #endif
