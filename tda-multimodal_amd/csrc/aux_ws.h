@@ -1,11 +1,11 @@
 // aux_ws.h -- the per-device workspace of the entries beside the persistence pipeline (UMAP, the
 // spectral metrics, greedy landmarks, resampling, the permutation test and the six diagram entries, which use it through dgm_call.h),
 // part of rips.hip's translation unit.  Each entry has a stream, buffers and a mutex of its own: no slot's stream is used and
-// nothing is captured into a graph.  The rules these entries share with the pipeline live here:
-// every allocation and free runs under g_capture_mu (never beside a slot's graph capture), a failed
-// growth leaves an empty buffer, and hipFuncSetAttribute runs once per workspace under g_attr_mu.
-// Lock order: an entry's w.mu, then g_capture_mu or g_attr_mu (never both); neither global lock
-// is held across a copy, a launch or a synchronise.
+// nothing is captured into a graph.  The rules these entries share with the pipeline live in ws_life.h
+// and are kept by calling it: a buffer grows through ws::grow (a failed growth leaves it empty) under
+// ws::AllocScope (never beside a slot's graph capture).  What is stated here only:
+// hipFuncSetAttribute runs once per workspace under g_attr_mu, which counts as a scope in
+// ws_life.h's lock order (an entry's w.mu, then one scope).
 #pragma once
 
 namespace {
@@ -17,10 +17,8 @@ struct AuxWs {
     hipStream_t stream = nullptr;
     hipEvent_t evin = nullptr;      // orders the stream after the caller's (aux_after_caller)
     hipEvent_t ev[4] = {};          // timing events (aux_events)
-    char* buf = nullptr;            // device
-    size_t cap = 0;
-    char* hout = nullptr;           // pinned and mapped
-    size_t hcap = 0;
+    ws::Buf<char> buf{ws::kDevice};
+    ws::Buf<char> hout{ws::kMapped};
     std::vector<const void*> attr;  // kernels whose dynamic-LDS limit is set (aux_lds_attr)
     std::mutex mu;                  // held for the whole call
 };
@@ -54,32 +52,21 @@ int aux_after_caller(AuxWs& w, void* caller) {
     return order_after_caller(w.stream, w.evin, caller, w.device);
 }
 
-// At least `bytes` of w.buf, then `also()` (a call's further allocations), in one hold of g_capture_mu.
+// At least `bytes` of w.buf, then `also()` (a call's further allocations), in one hold of the allocation scope.
 template <typename Also>
 int aux_reserve(AuxWs& w, size_t bytes, Also&& also) {
-    std::lock_guard<std::mutex> g(g_capture_mu);  // a free synchronises the device: never beside a slot's capture
-    if (w.cap < bytes) {
-        if (w.buf) HIPC(hipFree(w.buf));
-        w.buf = nullptr;
-        w.cap = 0;  // a failed allocation leaves an empty workspace, not a stale size
-        HIPC(hipMalloc(&w.buf, bytes));
-        w.cap = bytes;
-    }
+    ws::AllocScope lock;
+    if (int rc = ws::grow(g_hip, w.buf, bytes, bytes)) return rc;
     return also();
 }
 int aux_reserve(AuxWs& w, size_t bytes) {
-    return w.cap >= bytes ? 0 : aux_reserve(w, bytes, [] { return 0; });  // the lock on growth only
+    return w.buf.cap >= bytes ? 0 : aux_reserve(w, bytes, [] { return 0; });  // the lock on growth only
 }
 
 int aux_reserve_pinned(AuxWs& w, size_t bytes) {
-    if (w.hcap >= bytes) return 0;
-    std::lock_guard<std::mutex> g(g_capture_mu);
-    if (w.hout) HIPC(hipHostFree(w.hout));
-    w.hout = nullptr;
-    w.hcap = 0;
-    HIPC(hipHostMalloc((void**)&w.hout, bytes, hipHostMallocMapped));
-    w.hcap = bytes;
-    return 0;
+    if (w.hout.cap >= bytes) return 0;
+    ws::AllocScope lock;
+    return ws::grow(g_hip, w.hout, bytes, bytes);
 }
 
 // `fn` may be launched with up to `bytes` of dynamic LDS: set once per workspace (so once per device)

@@ -42,17 +42,17 @@ struct DgmCall {
             if (int rc = aux_lds_attr(*w, lds_fn, lds_bytes)) return rc;
         if (int rc = aux_reserve(*w, cv.o)) return rc;
         HIPC(hipEventRecord(w->ev[0], w->stream));
-        HIPC(hipMemcpyAsync(w->buf, host.data(), up_bytes, hipMemcpyHostToDevice, w->stream));
+        HIPC(hipMemcpyAsync(w->buf.p, host.data(), up_bytes, hipMemcpyHostToDevice, w->stream));
         return 0;
     }
     float ms = 0.0f;  // end: the device time between the two events
     hipStream_t stream() const { return w->stream; }
     template <typename T>
     T* at(size_t offset) const {
-        return (T*)(w->buf + offset);
+        return (T*)(w->buf.p + offset);
     }
     int end(void* dst, size_t offset, size_t bytes) {
-        HIPC(hipMemcpyAsync(dst, w->buf + offset, bytes, hipMemcpyDeviceToHost, w->stream));
+        HIPC(hipMemcpyAsync(dst, w->buf.p + offset, bytes, hipMemcpyDeviceToHost, w->stream));
         HIPC(hipEventRecord(w->ev[1], w->stream));
         HIPC(hipStreamSynchronize(w->stream));
         HIPC(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));

@@ -47,14 +47,14 @@ int ed_run(const EdJob& j, const Epi& epi, int64_t per_item, float* out) {
     const void* x = j.x;
     if (stage) {  // the kept rows of every item, packed: they then are (B, N, D)
         const size_t width = (size_t)j.keep_rows * D * esz;
-        HIPC(hipMemcpy2DAsync(w.buf + o_x, width, x, (size_t)j.src_rows * D * esz, width, (size_t)j.src_items,
+        HIPC(hipMemcpy2DAsync(w.buf.p + o_x, width, x, (size_t)j.src_rows * D * esz, width, (size_t)j.src_items,
                               j.x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        x = w.buf + o_x;
+        x = w.buf.p + o_x;
     } else if (!j.x_on_device) {
-        HIPC(hipMemcpyAsync(w.buf + o_x, x, (size_t)B * N * D * esz, hipMemcpyHostToDevice, s));
-        x = w.buf + o_x;
+        HIPC(hipMemcpyAsync(w.buf.p + o_x, x, (size_t)B * N * D * esz, hipMemcpyHostToDevice, s));
+        x = w.buf.p + o_x;
     }
-    double* G = (double*)(w.buf + o_g);
+    double* G = (double*)(w.buf.p + o_g);
     const bool f64 = j.dtype == TDA_F64;
     if (N <= D && D >= kDistMfmaMinD) {  // X X^T on the FP64 matrix cores
         const unsigned nt = (unsigned)((N + kDmT - 1) / kDmT);
@@ -76,8 +76,7 @@ int ed_run(const EdJob& j, const Epi& epi, int64_t per_item, float* out) {
         }
     }
     HIPC(hipGetLastError());
-    float* dout = nullptr;
-    HIPC(hipHostGetDevicePointer((void**)&dout, w.hout, 0));
+    float* dout = (float*)w.hout.dev;
     if (m <= kEdLdsMaxM) {
         if (int rc = aux_lds_attr(w, (const void*)k_ed_jacobi<true, Epi>, 8 * kEdLdsMaxM * kEdLdsMaxM)) return rc;
         hipLaunchKernelGGL((k_ed_jacobi<true, Epi>), dim3((unsigned)B), dim3(kEdT), (size_t)8 * m * m, s, G, (int)m, epi, dout);
@@ -86,7 +85,7 @@ int ed_run(const EdJob& j, const Epi& epi, int64_t per_item, float* out) {
     }
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(s));
-    std::memcpy(out, w.hout, sizeof(float) * n_out);
+    std::memcpy(out, w.hout.p, sizeof(float) * n_out);
     return 0;
 }
 

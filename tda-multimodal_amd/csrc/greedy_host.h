@@ -21,7 +21,7 @@ struct GreedyResultImpl {
     float* sub_dev = nullptr;
     ~GreedyResultImpl() {
         if (!sub_dev) return;
-        std::lock_guard<std::mutex> g(g_capture_mu);  // a free synchronises the device: never beside a slot's capture
+        ws::AllocScope lock;  // a free synchronises the device: never beside a slot's capture
         (void)hipFree(sub_dev);
     }
 };
@@ -88,30 +88,30 @@ extern "C" int tda_greedy_perm(const tda_greedy_args* a, tda_greedy_result** out
     R->idx.reset(new int64_t[L * k]);
     R->lam.reset(new float[L * k]);
     if (want_dp) R->dperm.reset(new float[L * k * N]);
-    const auto alloc_sub = [&]() -> int {  // the result's own buffer, in the same hold of g_capture_mu
+    const auto alloc_sub = [&]() -> int {  // the result's own buffer, in the same hold of the allocation scope
         HIPC(hipMalloc((void**)&R->sub_dev, L * k * k * 4));
         return 0;
     };
     if (int rc = aux_reserve(w, cv.o, alloc_sub)) return rc;
     if (a->x_on_device)
         if (int rc = aux_after_caller(w, a->stream)) return rc;
-    int64_t* d_idx = (int64_t*)(w.buf + o_idx);
-    float* d_lam = (float*)(w.buf + o_lam);
-    float* dm = (float*)(w.buf + o_dm);
-    float* d_dp = want_dp ? (float*)(w.buf + o_dp) : nullptr;
+    int64_t* d_idx = (int64_t*)(w.buf.p + o_idx);
+    float* d_lam = (float*)(w.buf.p + o_lam);
+    float* dm = (float*)(w.buf.p + o_dm);
+    float* d_dp = want_dp ? (float*)(w.buf.p + o_dp) : nullptr;
     double select_ms = 0.0;
     HIPC(hipEventRecord(ev0, s));
     for (size_t l0 = 0; l0 < L; l0 += Lc) {
         const size_t lc = std::min(Lc, L - l0);
         const void* x = (const char*)a->x + l0 * x_layer;
         if (host_in) {
-            HIPC(hipMemcpyAsync(w.buf + o_x, x, lc * x_layer, hipMemcpyHostToDevice, s));
-            x = w.buf + o_x;
+            HIPC(hipMemcpyAsync(w.buf.p + o_x, x, lc * x_layer, hipMemcpyHostToDevice, s));
+            x = w.buf.p + o_x;
         }
         if (!is_dist) {
-            HIPC(hipMemsetAsync(w.buf + o_rm, 0, lc * N * 4, s));  // the distance kernels fold row maxima in (unused here)
-            const DistLaunch dl = {x, a->dtype, n, a->D, (int)lc, sel, dm, (uint32_t*)(w.buf + o_rm), (double*)(w.buf + o_gp),
-                                   (double*)(w.buf + o_np), nullptr};
+            HIPC(hipMemsetAsync(w.buf.p + o_rm, 0, lc * N * 4, s));  // the distance kernels fold row maxima in (unused here)
+            const DistLaunch dl = {x, a->dtype, n, a->D, (int)lc, sel, dm, (uint32_t*)(w.buf.p + o_rm), (double*)(w.buf.p + o_gp),
+                                   (double*)(w.buf.p + o_np), nullptr};
             if (int rc = launch_point_distances(s, dl, [](const char*) { return 0; })) return rc;
         } else {
             const unsigned gx = (unsigned)std::min<uint64_t>(1024, ((uint64_t)N * N + 255) / 256);

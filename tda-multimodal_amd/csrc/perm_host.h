@@ -95,13 +95,13 @@ extern "C" int tda_permutation_test(const tda_perm_args* a, tda_perm_result** ou
     std::unique_ptr<PermResultImpl> R(new PermResultImpl());
     R->stat.reset(new double[rows]);
     if (int rc = aux_reserve(w, cv.o)) return rc;
-    const double* d_w = (const double*)(w.buf + o_w);
-    const double* d_c = (const double*)(w.buf + o_c);
-    double* d_out = (double*)(w.buf + o_out);
-    uint8_t* d_lab = (uint8_t*)(w.buf + o_lab);
+    const double* d_w = (const double*)(w.buf.p + o_w);
+    const double* d_c = (const double*)(w.buf.p + o_c);
+    double* d_out = (double*)(w.buf.p + o_out);
+    uint8_t* d_lab = (uint8_t*)(w.buf.p + o_lab);
     HIPC(hipEventRecord(ev0, s));
-    HIPC(hipMemcpyAsync(w.buf + o_w, a->w, S * S * 8, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(w.buf + o_c, cw, sizeof cw, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(w.buf.p + o_w, a->w, S * S * 8, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(w.buf.p + o_c, cw, sizeof cw, hipMemcpyHostToDevice, s));
     HIPC(hipMemcpyAsync(d_lab, a->lab, B * S, hipMemcpyHostToDevice, s));
     HIPC(hipMemcpyAsync(d_lab + B * S, a->obs, S, hipMemcpyHostToDevice, s));
     for (size_t r0 = 0; r0 < rows; r0 += chunk) {

@@ -85,9 +85,9 @@ extern "C" int tda_resample(const tda_resample_args* a, tda_resample_result** ou
     if (int rc = aux_reserve(w, cv.o)) return rc;
     if (a->x_on_device)
         if (int rc = aux_after_caller(w, a->stream)) return rc;
-    float* d_h = (float*)(w.buf + o_h);
-    int32_t* d_idx = (int32_t*)(w.buf + o_idx);
-    float* dm = (float*)(w.buf + o_dm);
+    float* d_h = (float*)(w.buf.p + o_h);
+    int32_t* d_idx = (int32_t*)(w.buf.p + o_idx);
+    float* dm = (float*)(w.buf.p + o_dm);
     const size_t idx_lstride = per_layer_idx ? B * m : 0;
     HIPC(hipEventRecord(ev0, s));
     if (!per_layer_idx) HIPC(hipMemcpyAsync(d_idx, a->idx, B * m * 4, hipMemcpyHostToDevice, s));
@@ -95,14 +95,14 @@ extern "C" int tda_resample(const tda_resample_args* a, tda_resample_result** ou
         const size_t lc = std::min(Lc, L - l0);
         const void* x = (const char*)a->x + l0 * x_layer;
         if (host_in) {
-            HIPC(hipMemcpyAsync(w.buf + o_x, x, lc * x_layer, hipMemcpyHostToDevice, s));
-            x = w.buf + o_x;
+            HIPC(hipMemcpyAsync(w.buf.p + o_x, x, lc * x_layer, hipMemcpyHostToDevice, s));
+            x = w.buf.p + o_x;
         }
         if (per_layer_idx) HIPC(hipMemcpyAsync(d_idx, a->idx + l0 * B * m, lc * B * m * 4, hipMemcpyHostToDevice, s));
         if (!is_dist) {
-            HIPC(hipMemsetAsync(w.buf + o_rm, 0, lc * N * 4, s));  // the distance kernels fold row maxima in (unused here)
-            const DistLaunch dl = {x, a->dtype, n, a->D, (int)lc, sel, dm, (uint32_t*)(w.buf + o_rm), (double*)(w.buf + o_gp),
-                                   (double*)(w.buf + o_np), nullptr};
+            HIPC(hipMemsetAsync(w.buf.p + o_rm, 0, lc * N * 4, s));  // the distance kernels fold row maxima in (unused here)
+            const DistLaunch dl = {x, a->dtype, n, a->D, (int)lc, sel, dm, (uint32_t*)(w.buf.p + o_rm), (double*)(w.buf.p + o_gp),
+                                   (double*)(w.buf.p + o_np), nullptr};
             if (int rc = launch_point_distances(s, dl, [](const char*) { return 0; })) return rc;
         } else {
             const unsigned gx = (unsigned)std::min<uint64_t>(1024, ((uint64_t)N * N + 255) / 256);

@@ -26,7 +26,6 @@
 #include <cstring>
 #include <memory>
 #include <mutex>
-#include <shared_mutex>
 #include <string>
 #include <vector>
 
@@ -37,6 +36,7 @@
 #include "rips_reduce_small.h"
 #include "rips_retry.h"
 #include "rips_plan.h"
+#include "ws_life.h"
 
 using namespace tda;
 
@@ -78,6 +78,24 @@ int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess) return fail(TDA_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// The runtime of ws_life.h: each call forwarded to HIP and nothing else.  Buffers, graphs and
+// captures are made and destroyed through it only (besides check_layout's probe buffer and the
+// result buffer of tda_greedy_perm, which its caller owns).
+struct HipRt {
+    int host_alloc(void** p, size_t bytes, bool mapped) { return hipHostMalloc(p, bytes, mapped ? hipHostMallocMapped : hipHostMallocDefault); }
+    int alloc(ws::Mem m, void** p, size_t bytes) { return m == ws::kDevice ? hipMalloc(p, bytes) : host_alloc(p, bytes, m == ws::kMapped); }
+    int free(ws::Mem m, void* p) { return m == ws::kDevice ? hipFree(p) : hipHostFree(p); }
+    int alias(void** dev, void* host) { return hipHostGetDevicePointer(dev, host, 0); }
+    int begin_capture(void* s) { return hipStreamBeginCapture((hipStream_t)s, hipStreamCaptureModeThreadLocal); }
+    int end_capture(void* s, void** graph) { return hipStreamEndCapture((hipStream_t)s, (hipGraph_t*)graph); }
+    int instantiate(void** exec, void* graph) { return hipGraphInstantiate((hipGraphExec_t*)exec, (hipGraph_t)graph, nullptr, nullptr, 0); }
+    int launch(void* exec, void* s) { return hipGraphLaunch((hipGraphExec_t)exec, (hipStream_t)s); }
+    int destroy_exec(void* exec) { return hipGraphExecDestroy((hipGraphExec_t)exec); }
+    int destroy_graph(void* graph) { return hipGraphDestroy((hipGraph_t)graph); }
+    int record(void* ev, void* s) { return hipEventRecord((hipEvent_t)ev, (hipStream_t)s); }
+    int fail(const char* call, int e) { return ::fail(TDA_E_HIP, std::string(call) + ": " + hipGetErrorString((hipError_t)e)); }
+} g_hip;
+
 // ------------------------------------------------------------------ workspace
 struct Workspace {
     int device = -1;
@@ -85,40 +103,27 @@ struct Workspace {
     bool init = false;
     hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr, stream4 = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evf = nullptr, evj = nullptr, evs = nullptr, evp = nullptr, evh = nullptr, evsil = nullptr;
-    char* dbuf = nullptr;
-    size_t dcap = 0;
-    OutPair* hout = nullptr;  // host-mapped
-    OutPair* hout_dev = nullptr;
-    size_t hout_cap = 0;      // in pairs
-    LayerStats* hstats = nullptr;  // host-mapped: k_emit writes it
+    // captured launch sequences; its gen() rises whenever a buffer baked into graphs moves
+    ws::GraphCache graphs;
+    // the buffers (ws_life.h: p, its device alias dev, cap in elements); all but hdist are baked into the graphs
+    ws::Buf<char> dbuf{ws::kDevice, &graphs};
+    ws::Buf<OutPair> hout{ws::kMapped, &graphs};
+    ws::Buf<LayerStats> hstats{ws::kMapped, &graphs};  // k_emit writes it
+    ws::Buf<int64_t> houtoff{ws::kMapped, &graphs};
+    ws::Buf<char> hsil{ws::kMapped, &graphs};   // silhouette labels [S][N] i32, then scores [L][S] f64
+    ws::Buf<float> htn{ws::kMapped, &graphs};   // TwoNN estimates [L] (k_twonn writes them)
+    ws::Buf<char> hin{ws::kPinned, &graphs};    // staging of host inputs (stable graph source)
+    ws::Buf<char> hdist{ws::kPinned};           // landing of the distance matrices (want_dist: f32, then f64)
+    ws::Buf<char> xin{ws::kDevice, &graphs};    // gathered device input parts (ABI 6 x_parts)
     // sparse-cleared H2 pivot bitmap (Plan::piv2_sparse): the region known to be zero
     bool piv2_dirty = true;
     char* piv2_ptr = nullptr;
     size_t piv2_bytes = 0;
-    char* hsil = nullptr;          // host-mapped: silhouette labels [S][N] i32, then scores [L][S] f64
-    char* hsil_dev = nullptr;
-    size_t hsil_cap = 0;
-    float* htn = nullptr;          // host-mapped: TwoNN estimates [L] (k_twonn writes them)
-    float* htn_dev = nullptr;
-    size_t htn_cap = 0;
-    LayerStats* hstats_dev = nullptr;
-    int64_t* houtoff_dev = nullptr;
-    size_t hstats_cap = 0;
-    int64_t* houtoff = nullptr;
-    size_t houtoff_cap = 0;
     std::vector<hipEvent_t> stage_ev;  // stage-time events (TDA_FLAG_STAGE_TIMES)
     std::vector<hipEvent_t> stage_ev2; // ... on the side stream
     std::vector<hipEvent_t> stage_ev3; // ... on the third stream
     std::vector<hipEvent_t> stage_ev4; // ... on the fourth stream
     hipEvent_t evin = nullptr;         // caller's stream -> library stream
-    char* hin = nullptr;               // pinned staging of host inputs (stable graph source)
-    size_t hin_cap = 0;
-    char* hdist = nullptr;             // pinned landing of the distance matrices (want_dist: f32, then f64)
-    size_t hdist_cap = 0;
-    void* xin = nullptr;  // gathered device input parts (ABI 6 x_parts)
-    size_t xin_cap = 0;
-    uint64_t gen = 0;                  // bumped whenever a buffer baked into graphs moves
-    std::vector<struct GraphEntry> graphs;
     // the configuration a retry ended on (larger pools / another reducer), per
     // (N, maxdim, input kind): later calls of that shape start there instead of
     // failing the same way first
@@ -129,24 +134,6 @@ struct Workspace {
     };
     std::vector<Retry> retry;
     std::mutex mu;
-};
-
-// one captured launch sequence (everything between ev0 and ev1), replayed with
-// a single hipGraphLaunch when the same plan, input address and flags recur
-struct GraphKey {
-    int64_t L, N, D;
-    int maxdim, dtype, input_kind, x_on_device, flags, force_global, scale, force_big, variant, n_label_sets, sil_K, no_par, twonn, no_cap;
-    int dsplit;  // K slices of the distance kernels (TDA_DIST_SPLIT can change them at the same (N, D): other launches, other offsets)
-    float thresh, tn_eps, capf;
-    double tn_discard;
-    const void* x;
-    uint64_t gen;
-    bool operator==(const GraphKey& o) const { return std::memcmp(this, &o, sizeof(GraphKey)) == 0; }
-};
-struct GraphEntry {
-    GraphKey key;
-    hipGraphExec_t exec;
-    hipGraph_t graph;  // kept as long as its exec (r06: see the capture below)
 };
 
 // records an event after each stage when stage timing is on
@@ -247,25 +234,6 @@ int order_after_caller(hipStream_t lib, hipEvent_t ev, void* caller, int dev) {
 }
 
 std::mutex g_ws_mu;
-// Graph capture + instantiation AND every workspace (re)allocation / free, across
-// all slots of the process.  r03 saw a host segfault inside the first calls of
-// two slots that ran concurrently; the cause was not isolated then.  The HIP
-// calls those first calls made at the same time were: hipFuncSetAttribute
-// (one-time, now under g_attr_mu), stream capture + hipGraphInstantiate on
-// the two slots' streams, and hipMalloc / hipHostMalloc of the workspaces --
-// and on growth hipFree / hipHostFree / hipGraphExecDestroy.  ThreadLocal
-// capture only restricts the CAPTURING thread, and HIP's hipFree synchronises
-// the whole device (all streams, a capturing one included) while another
-// thread captures; it is the one call whose contract does not cover running
-// beside a capture.  So no (re)allocation, free or graph destruction runs
-// while any slot captures: they take this lock too (first call / growth only;
-// replays never take it).
-std::mutex g_capture_mu;
-// Graph launches: replays (and direct launches) share it; a capture with its instantiation and
-// first launch holds it alone.  r06 (tools/concurrency_stress.py: 8 slots, calls of mixed shapes
-// at once): a freshly instantiated graph's first hipGraphLaunch faulted inside the HIP runtime
-// (a null dereference) while other slots replayed theirs; one slot at a time never did.
-std::shared_mutex g_launch_mu;
 std::vector<Workspace*> g_ws;
 
 Workspace* get_ws(int dev, int slot) {
@@ -277,15 +245,6 @@ Workspace* get_ws(int dev, int slot) {
     w->slot = slot;
     g_ws.push_back(w);
     return w;
-}
-
-void drop_graphs(Workspace& w) {
-    for (auto& g : w.graphs) {
-        (void)hipGraphExecDestroy(g.exec);
-        (void)hipGraphDestroy(g.graph);
-    }
-    w.graphs.clear();
-    ++w.gen;
 }
 
 // ------------------------------------------------------------------ build consistency
@@ -363,57 +322,22 @@ int ws_prepare(Workspace& w, const Plan& p) {
         if (int rc = check_layout(w.stream)) return rc;
         w.init = true;
     }
-    if (w.dcap < p.total) {
-        drop_graphs(w);
-        w.piv2_dirty = true;
-        if (w.dbuf) HIPC(hipFree(w.dbuf));
-        w.dbuf = nullptr;
-        size_t cap = std::max<size_t>(p.total, w.dcap + w.dcap / 2);
-        if (hipMalloc(&w.dbuf, cap) != hipSuccess) {
-            (void)hipGetLastError();
-            size_t fr = 0, tot = 0;
-            (void)hipMemGetInfo(&fr, &tot);
-            w.dbuf = nullptr;
-            w.dcap = 0;
-            return fail(TDA_E_HIP, "device workspace of " + std::to_string(cap >> 20) + " MiB does not fit (free " +
-                                       std::to_string(fr >> 20) + " of " + std::to_string(tot >> 20) + " MiB)");
-        }
-        w.dcap = cap;
+    if (w.dbuf.cap < p.total) w.piv2_dirty = true;
+    const size_t cap = ws::want_half_more(p.total, w.dbuf.cap);
+    ws::GrowStep step;
+    if (int rc = ws::grow(g_hip, w.dbuf, p.total, cap, &step)) {
+        if (step != ws::kGrowAlloc) return rc;
+        (void)hipGetLastError();
+        size_t fr = 0, tot = 0;
+        (void)hipMemGetInfo(&fr, &tot);
+        return fail(TDA_E_HIP, "device workspace of " + std::to_string(cap >> 20) + " MiB does not fit (free " +
+                                   std::to_string(fr >> 20) + " of " + std::to_string(tot >> 20) + " MiB)");
     }
-    if (w.hstats_cap < (size_t)p.L) {
-        drop_graphs(w);
-        if (w.hstats) HIPC(hipHostFree(w.hstats));
-        HIPC(hipHostMalloc((void**)&w.hstats, sizeof(LayerStats) * p.L, hipHostMallocMapped));
-        HIPC(hipHostGetDevicePointer((void**)&w.hstats_dev, w.hstats, 0));
-        w.hstats_cap = p.L;
-    }
-    if (w.houtoff_cap < (size_t)p.L * 4) {
-        drop_graphs(w);
-        if (w.houtoff) HIPC(hipHostFree(w.houtoff));
-        HIPC(hipHostMalloc((void**)&w.houtoff, sizeof(int64_t) * p.L * 4, hipHostMallocMapped));
-        HIPC(hipHostGetDevicePointer((void**)&w.houtoff_dev, w.houtoff, 0));
-        w.houtoff_cap = p.L * 4;
-    }
-    size_t want = std::max<size_t>(1 << 16, (size_t)p.L * 256);
-    if (w.hout_cap < want) {
-        drop_graphs(w);
-        if (w.hout) HIPC(hipHostFree(w.hout));
-        HIPC(hipHostMalloc((void**)&w.hout, sizeof(OutPair) * want, hipHostMallocMapped));
-        HIPC(hipHostGetDevicePointer((void**)&w.hout_dev, w.hout, 0));
-        w.hout_cap = want;
-    }
-    return 0;
-}
-
-int grow_hout(Workspace& w, size_t need) {
-    drop_graphs(w);
-    if (w.hout) HIPC(hipHostFree(w.hout));
-    w.hout = nullptr;
-    size_t cap = std::max(need, 2 * w.hout_cap);
-    HIPC(hipHostMalloc((void**)&w.hout, sizeof(OutPair) * cap, hipHostMallocMapped));
-    HIPC(hipHostGetDevicePointer((void**)&w.hout_dev, w.hout, 0));
-    w.hout_cap = cap;
-    return 0;
+    const size_t L = (size_t)p.L;
+    if (int rc = ws::grow(g_hip, w.hstats, L, L)) return rc;
+    if (int rc = ws::grow(g_hip, w.houtoff, L * 4, L * 4)) return rc;
+    const size_t want = ws::want_floor(L * 256, ws::kFloorStage);
+    return ws::grow(g_hip, w.hout, want, want);
 }
 
 bool g_attr_done[64] = {false};
@@ -624,26 +548,6 @@ int rerun_cap_missed(const tda_rips_args& a, int input_kind, const void* host_or
     return 0;
 }
 
-// Grows one per-call buffer of the workspace to `need` elements of `elem` bytes (at least
-// `floor`).  baked: captured graphs hold its address, so they are dropped with it.  Mapped
-// buffers refresh their device pointer.  Called under g_capture_mu (a free synchronises the device).
-enum BufMem { kPinned, kMapped, kDevice };
-int grow_buf(Workspace& w, void** buf, size_t& cap, size_t need, size_t floor, size_t elem, BufMem mem, bool baked, void** dev_ptr) {
-    if (cap >= need) return 0;
-    if (baked) drop_graphs(w);
-    if (*buf) HIPC(mem == kDevice ? hipFree(*buf) : hipHostFree(*buf));
-    *buf = nullptr;
-    cap = 0;
-    const size_t want = std::max(need, floor);
-    if (mem == kDevice)
-        HIPC(hipMalloc(buf, want * elem));
-    else
-        HIPC(hipHostMalloc(buf, want * elem, mem == kMapped ? hipHostMallocMapped : hipHostMallocDefault));
-    if (mem == kMapped) HIPC(hipHostGetDevicePointer(dev_ptr, *buf, 0));
-    cap = want;
-    return 0;
-}
-
 // silhouette labels: every set must be codes 0..K-1, all used, 2 <= K <= n - 1 (sklearn); sil_K: the largest K
 int validate_labels(const tda_rips_args& a, int n, int nls, int& sil_K) {
     for (int q = 0; q < nls; ++q) {
@@ -666,7 +570,7 @@ int validate_labels(const tda_rips_args& a, int n, int nls, int& sil_K) {
 
 // The workspace sized for this call's plan and arguments, and the call's view of it.  Allocations,
 // frees and graph drops (first call / growth) never overlap another slot's capture: the caller
-// holds g_capture_mu, and releases it before the input copies (the host-input memcpy
+// holds ws::AllocScope, and releases it before the input copies (the host-input memcpy
 // serialised pipelined slots).
 int prepare_buffers(Call& c) {
     const tda_rips_args& a = c.a;
@@ -675,7 +579,7 @@ int prepare_buffers(Call& c) {
     if (int rc = ws_prepare(w, p)) return rc;
     if (int rc = set_lds_attrs(a.device)) return rc;
     c.s = w.stream;
-    c.B = w.dbuf;
+    c.B = w.dbuf.p;
     const int n = c.n = (int)p.N, L = c.L = (int)p.L;
     c.dist = (float*)(c.B + p.o_dist);
     c.stats = (LayerStats*)(c.B + p.o_stats);
@@ -697,13 +601,13 @@ int prepare_buffers(Call& c) {
     // want_dist: the matrices come back by an async copy queued behind the call's work (one
     // stream sync for both; r06: a blocking hipMemcpy after the sync cost ~20 us per small call)
     c.dbytes = a.want_dist ? (size_t)L * n * n * (4 + (p.want64 ? 8 : 0)) : 0;
-    if (int rc = grow_buf(w, (void**)&w.hdist, w.hdist_cap, c.dbytes, 1 << 16, 1, kPinned, false, nullptr)) return rc;
+    if (int rc = ws::grow(g_hip, w.hdist, c.dbytes, ws::want_floor(c.dbytes, ws::kFloorStage))) return rc;
     if (c.host_in) {
-        if (int rc = grow_buf(w, (void**)&w.hin, w.hin_cap, c.xbytes, 1 << 16, 1, kPinned, true, nullptr)) return rc;
-        c.xsrc = w.hin;
+        if (int rc = ws::grow(g_hip, w.hin, c.xbytes, ws::want_floor(c.xbytes, ws::kFloorStage))) return rc;
+        c.xsrc = w.hin.p;
     } else if (c.dev_parts) {
-        if (int rc = grow_buf(w, &w.xin, w.xin_cap, c.xbytes, 0, 1, kDevice, true, nullptr)) return rc;
-        c.xsrc = w.xin;
+        if (int rc = ws::grow(g_hip, w.xin, c.xbytes, c.xbytes)) return rc;
+        c.xsrc = w.xin.p;
     }
 
     // silhouette labels -> host-mapped buffer (stable address: a graph source)
@@ -712,14 +616,14 @@ int prepare_buffers(Call& c) {
         if (int rc = validate_labels(a, n, c.nls, c.sil_K)) return rc;
         c.sil_out_off = align_up((size_t)c.nls * n * 4, 16);
         const size_t need = c.sil_out_off + (size_t)L * c.nls * 8;
-        if (int rc = grow_buf(w, (void**)&w.hsil, w.hsil_cap, need, 1 << 12, 1, kMapped, true, (void**)&w.hsil_dev)) return rc;
+        if (int rc = ws::grow(g_hip, w.hsil, need, ws::want_floor(need, ws::kFloorSil))) return rc;
     }
 
     // TwoNN estimates -> host-mapped buffer (stable address: a graph source)
     c.want_tn = a.want_twonn != 0;
     c.no_ph = (a.flags & TDA_FLAG_NO_PERSISTENCE) != 0;
     if (c.want_tn)
-        if (int rc = grow_buf(w, (void**)&w.htn, w.htn_cap, (size_t)L, 64, sizeof(float), kMapped, true, (void**)&w.htn_dev)) return rc;
+        if (int rc = ws::grow(g_hip, w.htn, (size_t)L, ws::want_floor((size_t)L, ws::kFloorTn))) return rc;
 
     // TDA_FLAG_STAGE_SERIAL (with stage times) or TDA_FLAG_ONE_STREAM: every
     // stage on the main stream -- each pair of stage events then brackets one
@@ -731,7 +635,7 @@ int prepare_buffers(Call& c) {
     return 0;
 }
 
-// input copies and ordering, outside g_capture_mu
+// input copies and ordering, outside any lock scope
 int stage_inputs(Call& c) {
     const tda_rips_args& a = c.a;
     Workspace& w = c.w;
@@ -740,9 +644,9 @@ int stage_inputs(Call& c) {
     if (c.host_in) {
         if (c.nparts > 0) {  // parts: one after the other into the staging buffer
             const size_t pb = c.xbytes / c.nparts;
-            for (int i = 0; i < c.nparts; ++i) std::memcpy((char*)w.hin + i * pb, a.x_parts[i], pb);
+            for (int i = 0; i < c.nparts; ++i) std::memcpy(w.hin.p + i * pb, a.x_parts[i], pb);
         } else if (c.xbytes) {
-            std::memcpy(w.hin, c.host_or_dev, c.xbytes);
+            std::memcpy(w.hin.p, c.host_or_dev, c.xbytes);
         }
     } else if (c.dev_parts) {
         // device parts: gathered into the workspace's own input buffer by one kernel on the
@@ -751,10 +655,10 @@ int stage_inputs(Call& c) {
         for (int i = 0; i < c.nparts; ++i) pl.p[i] = a.x_parts[i];
         const uint64_t words = c.xbytes / c.nparts / 4;
         const unsigned gx = (unsigned)std::min<uint64_t>(64, (words + 255) / 256);
-        hipLaunchKernelGGL(k_gather_parts, dim3(std::max(1u, gx), c.nparts), dim3(256), 0, c.s, pl, words, (uint32_t*)w.xin);
+        hipLaunchKernelGGL(k_gather_parts, dim3(std::max(1u, gx), c.nparts), dim3(256), 0, c.s, pl, words, (uint32_t*)w.xin.p);
         HIPC(hipGetLastError());
     }
-    if (c.nls) std::memcpy(w.hsil, a.labels, (size_t)c.nls * c.n * 4);
+    if (c.nls) std::memcpy(w.hsil.p, a.labels, (size_t)c.nls * c.n * 4);
     return 0;
 }
 
@@ -769,7 +673,7 @@ struct StreamSwap {
 };
 
 // what a captured launch sequence depends on; also settles the two switches that are part of it
-void fill_graph_key(Call& c, GraphKey& gk) {
+void fill_graph_key(Call& c, ws::GraphKey& key) {
     const tda_rips_args& a = c.a;
     const Plan& p = c.p;
     c.dist_mfma = p.dist.mfma;
@@ -779,90 +683,46 @@ void fill_graph_key(Call& c, GraphKey& gk) {
     // abort): that kernel reads every layer's H1 pivots, so no layer's H1 may be left unfinished
     const bool h2_serial = p.par && p.maxdim >= 2 && !p.par2;
     c.capf = (c.at.no_cap || h2_serial || !(std::isinf(a.thresh) || a.thresh == 3.402823466e+38f)) ? 0.0f : par_capf();
-    std::memset(&gk, 0, sizeof(gk));
-    gk.L = p.L;
-    gk.N = p.N;
-    gk.D = p.D;
-    gk.maxdim = p.maxdim;
-    gk.dtype = p.dtype;
-    gk.input_kind = c.input_kind;
-    gk.x_on_device = a.x_on_device;
-    gk.flags = a.flags;
-    gk.force_global = c.at.force_global;
-    gk.scale = c.at.scale;
-    gk.force_big = c.at.force_big;
-    gk.no_par = c.at.no_par;
-    gk.no_cap = c.at.no_cap;
-    gk.capf = c.capf;
-    gk.variant = (p.dense ? 1 : 0) | (p.big ? 2 : 0) | (p.fast ? 4 : 0) | (p.lds_mode ? 8 : 0) | (p.cmode << 4) | (p.par ? 1 << 8 : 0) | (c.dist_mfma ? 1 << 9 : 0) |
-                 (p.wide ? 1 << 10 : 0) | (p.want64 ? 1 << 11 : 0) | (p.par2 ? 1 << 12 : 0) | (p.piv2_sparse ? 1 << 13 : 0) |
-                 (p.dist.gram_layer ? 1 << 14 : 0);
-    gk.dsplit = p.dist.dsplit;
-    gk.thresh = a.thresh;
-    gk.n_label_sets = c.nls;
-    gk.sil_K = c.sil_K;  // baked into the k_silhouette launch (argument K and its LDS size)
-    gk.twonn = c.want_tn;
-    gk.tn_discard = c.want_tn ? a.twonn_discard : 0.0;
-    gk.tn_eps = c.want_tn ? a.twonn_eps : 0.0f;
-    gk.x = c.xsrc;
-    gk.gen = c.w.gen;
+    ws::make_key(key, [&](ws::GraphKey& gk) {
+        gk.L = p.L;
+        gk.N = p.N;
+        gk.D = p.D;
+        gk.maxdim = p.maxdim;
+        gk.dtype = p.dtype;
+        gk.input_kind = c.input_kind;
+        gk.x_on_device = a.x_on_device;
+        gk.flags = a.flags;
+        gk.force_global = c.at.force_global;
+        gk.scale = c.at.scale;
+        gk.force_big = c.at.force_big;
+        gk.no_par = c.at.no_par;
+        gk.no_cap = c.at.no_cap;
+        gk.capf = c.capf;
+        gk.variant = (p.dense ? 1 : 0) | (p.big ? 2 : 0) | (p.fast ? 4 : 0) | (p.lds_mode ? 8 : 0) | (p.cmode << 4) | (p.par ? 1 << 8 : 0) | (c.dist_mfma ? 1 << 9 : 0) |
+                     (p.wide ? 1 << 10 : 0) | (p.want64 ? 1 << 11 : 0) | (p.par2 ? 1 << 12 : 0) | (p.piv2_sparse ? 1 << 13 : 0) |
+                     (p.dist.gram_layer ? 1 << 14 : 0);
+        gk.dsplit = p.dist.dsplit;
+        gk.thresh = a.thresh;
+        gk.n_label_sets = c.nls;
+        gk.sil_K = c.sil_K;  // baked into the k_silhouette launch (argument K and its LDS size)
+        gk.twonn = c.want_tn;
+        gk.tn_discard = c.want_tn ? a.twonn_discard : 0.0;
+        gk.tn_eps = c.want_tn ? a.twonn_eps : 0.0f;
+        gk.x = c.xsrc;
+        gk.gen = c.w.graphs.gen();
+    });
 }
 
 // The call's launch sequence on the device: a replay of the graph captured for this key, else a
 // capture (instantiated, kept and launched), else -- stage-timed calls, TDA_GRAPH=0 -- eagerly.
-int launch_or_capture(Call& c, const GraphKey& gk) {
-    Workspace& w = c.w;
-    hipStream_t s = c.s;
-    GraphEntry* ge = nullptr;
+int launch_or_capture(Call& c, const ws::GraphKey& gk) {
     // stage-timed calls run eagerly: timing events inside a capture need
     // external event nodes, which torch's bundled HIP runtime rejects
     const bool use_graph = !test_env_is("TDA_GRAPH", "0") && !c.tm.on;
-    if (use_graph)
-        for (auto& g : w.graphs)
-            if (g.key == gk) ge = &g;
-    c.capture = use_graph && !ge;
-    if (ge) {
-        std::shared_lock<std::shared_mutex> launch_lock(g_launch_mu);
-        HIPC(hipEventRecord(w.ev0, s));
-        HIPC(hipGraphLaunch(ge->exec, s));
-        HIPC(hipEventRecord(w.ev1, s));
-    } else if (c.capture) {
-        // capture + instantiate one graph at a time across the process: concurrent
-        // captures from several slot threads crashed the HIP runtime once (r03, host
-        // segfault inside a first call of two slots); replays run concurrently with each
-        // other, but not with a capture and its first launch (g_launch_mu)
-        std::lock_guard<std::mutex> cap_lock(g_capture_mu);
-        std::unique_lock<std::shared_mutex> launch_lock(g_launch_mu);
-        HIPC(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue_schedule(c);
-        hipGraph_t graph = nullptr;
-        const hipError_t ce = hipStreamEndCapture(s, &graph);
-        if (rc) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc;
-        }
-        if (ce != hipSuccess) return fail(TDA_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-        GraphEntry e;
-        e.key = gk;
-        e.graph = graph;
-        // the captured graph lives as long as its executable instance: destroying it right after
-        // hipGraphInstantiate (legal by the API) faulted in the instance's first hipGraphLaunch
-        // when other slots' threads were calling at the same time (r06, tools/concurrency_stress.py)
-        const hipError_t ie = hipGraphInstantiate(&e.exec, graph, nullptr, nullptr, 0);
-        if (ie != hipSuccess) {
-            (void)hipGraphDestroy(graph);
-            return fail(TDA_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
-        }
-        if (w.graphs.size() >= 16) drop_graphs(w), e.key.gen = w.gen;
-        w.graphs.push_back(e);
-        HIPC(hipEventRecord(w.ev0, s));
-        HIPC(hipGraphLaunch(w.graphs.back().exec, s));
-        HIPC(hipEventRecord(w.ev1, s));
-    } else {
-        std::shared_lock<std::shared_mutex> launch_lock(g_launch_mu);
-        if (int rc = enqueue_schedule(c)) return rc;
-    }
-    return 0;
+    return ws::launch(g_hip, c.w.graphs, gk, use_graph, c.s, c.w.ev0, c.w.ev1, [&](bool capture) {
+        c.capture = capture;
+        return enqueue_schedule(c);
+    });
 }
 
 // After the call's synchronisation: the layers' error flags OR-ed (without ERR_CAP_MISS).  An
@@ -872,10 +732,10 @@ int collect_errors(Call& c, int& errs) {
     Workspace& w = c.w;
     const int L = c.L;
     errs = 0;
-    for (int l = 0; l < L; ++l) errs |= w.hstats[l].err & ~ERR_CAP_MISS;
+    for (int l = 0; l < L; ++l) errs |= w.hstats.p[l].err & ~ERR_CAP_MISS;
     if (p.piv2_sparse) {  // clean again unless a layer's word list overflowed
         bool over = false;
-        for (int l = 0; l < L; ++l) over |= (uint64_t)w.hstats[l].n_clr2 > p.clr_cap;
+        for (int l = 0; l < L; ++l) over |= (uint64_t)w.hstats.p[l].n_clr2 > p.clr_cap;
         // only k_apparent<2> lists the words it sets: when H2 was reduced by k_reduce_big<2>
         // (TDA_PAR2=0, or no_par >= 1 after a k_reduce_par abort) that kernel also set residual-pivot
         // bits nobody listed, so the next call must start from a full memset
@@ -884,18 +744,18 @@ int collect_errors(Call& c, int& errs) {
     if (errs == ERR_OUT_CAP) {
         size_t need = 0;
         for (int l = 0; l < L; ++l)
-            for (int d = 0; d <= p.maxdim; ++d) need += (size_t)std::min<uint64_t>(w.hstats[l].count[d], p.pcap[d]);
+            for (int d = 0; d <= p.maxdim; ++d) need += (size_t)std::min<uint64_t>(w.hstats.p[l].count[d], p.pcap[d]);
         {
-            std::lock_guard<std::mutex> g(g_capture_mu);
-            if (int rc = grow_hout(w, need + 16)) return rc;
+            ws::AllocScope lock;
+            if (int rc = ws::grow(g_hip, w.hout, need + 16, ws::want_double(need + 16, w.hout.cap))) return rc;
         }
-        for (int l = 0; l < L; ++l) w.hstats[l].err = 0;
-        HIPC(hipMemcpyAsync(c.stats, w.hstats, sizeof(LayerStats) * L, hipMemcpyHostToDevice, c.s));
+        for (int l = 0; l < L; ++l) w.hstats.p[l].err = 0;
+        HIPC(hipMemcpyAsync(c.stats, w.hstats.p, sizeof(LayerStats) * L, hipMemcpyHostToDevice, c.s));
         launch_k_emit(c);
         HIPC(hipGetLastError());
         HIPC(hipStreamSynchronize(c.s));
         errs = 0;
-        for (int l = 0; l < L; ++l) errs |= w.hstats[l].err & ~ERR_CAP_MISS;
+        for (int l = 0; l < L; ++l) errs |= w.hstats.p[l].err & ~ERR_CAP_MISS;
     }
     return 0;
 }
@@ -948,7 +808,7 @@ ResultImpl* build_result(Call& c) {
     const size_t S = (size_t)L * nd;
     size_t total = 0;
     for (int l = 0; l < L; ++l)
-        for (int d = 0; d < nd; ++d) total += (size_t)std::min<int64_t>(w.hstats[l].count[d], (int64_t)p.pcap[d]);
+        for (int d = 0; d < nd; ++d) total += (size_t)std::min<int64_t>(w.hstats.p[l].count[d], (int64_t)p.pcap[d]);
     const size_t o_ne = 7 * S, o_idx = o_ne + L, o_thr = o_idx + 2 * total, o_bd = o_thr + (L + 1) / 2;
     R->blob.assign(o_bd + total, 0);
     int64_t* m_count = (int64_t*)R->blob.data();
@@ -966,7 +826,7 @@ ResultImpl* build_result(Call& c) {
     // at houtoff, in layer order (k_emit)
     size_t e = 0;
     for (int l = 0; l < L; ++l) {
-        const LayerStats& st = w.hstats[l];
+        const LayerStats& st = w.hstats.p[l];
         r_thr[l] = st.thresh;
         r_ne[l] = st.num_edges;
         for (int d = 0; d < nd; ++d) {
@@ -978,9 +838,9 @@ ResultImpl* build_result(Call& c) {
             m_cols[l * nd + d] = st.n_columns[d];
             m_res[l * nd + d] = st.n_residual[d] - st.nskip[d];
             m_add[l * nd + d] = st.n_adds[d];
-            const size_t src = (size_t)w.houtoff[l * nd + d];
+            const size_t src = (size_t)w.houtoff.p[l * nd + d];
             for (size_t i = 0; i < cnt; ++i, ++e) {
-                const OutPair q = w.hout[src + i];
+                const OutPair q = w.hout.p[src + i];
                 r_bd[e] = q.birth;
                 r_bd[total + e] = q.death;
                 r_idx[e] = q.birth_idx;
@@ -995,22 +855,22 @@ ResultImpl* build_result(Call& c) {
     point_result(*R, total);
     if (a.want_dist) {  // landed by the async copies behind the call (synchronised by the caller)
         R->dist.resize((size_t)L * n * n);
-        std::memcpy(R->dist.data(), w.hdist, sizeof(float) * L * n * n);
+        std::memcpy(R->dist.data(), w.hdist.p, sizeof(float) * L * n * n);
     }
     if (p.want64) {
         R->dist64.resize((size_t)L * n * n);
-        std::memcpy(R->dist64.data(), w.hdist + sizeof(float) * L * n * n, sizeof(double) * L * n * n);
+        std::memcpy(R->dist64.data(), w.hdist.p + sizeof(float) * L * n * n, sizeof(double) * L * n * n);
     }
     o.dist = a.want_dist ? R->dist.data() : nullptr;
     o.dist64 = p.want64 ? R->dist64.data() : nullptr;
     o.silhouette = nullptr;
     if (c.nls) {
-        R->sil.assign((const double*)(w.hsil + c.sil_out_off), (const double*)(w.hsil + c.sil_out_off) + (size_t)L * c.nls);
+        R->sil.assign((const double*)(w.hsil.p + c.sil_out_off), (const double*)(w.hsil.p + c.sil_out_off) + (size_t)L * c.nls);
         o.silhouette = R->sil.data();
     }
     o.twonn = nullptr;
     if (c.want_tn) {
-        R->tn.assign(w.htn, w.htn + L);
+        R->tn.assign(w.htn.p, w.htn.p + L);
         o.twonn = R->tn.data();
     }
     float ms = 0.0f;
@@ -1072,7 +932,7 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
                     input_kind == 0 && a.dtype == TDA_F64 && a.want_dist && (a.flags & TDA_FLAG_DIST64), at);
     const Plan& p = c.p;
     {
-        std::lock_guard<std::mutex> rt_lock(g_capture_mu);  // buffers in place; a capture re-takes it
+        ws::AllocScope lock;  // buffers in place; a capture re-takes it
         if (int rc = prepare_buffers(c)) return rc;
     }
     if (int rc = stage_inputs(c)) return rc;
@@ -1084,7 +944,7 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
     c.tm.s = s, c.tm2.s = w.stream2, c.tm3.s = w.stream3, c.tm4.s = w.stream4;
     c.tm.on = c.tm2.on = c.tm3.on = c.tm4.on = (a.flags & TDA_FLAG_STAGE_TIMES) != 0;
     if (c.serial_stages) c.tm2.fwd = c.tm3.fwd = c.tm4.fwd = &c.tm;
-    GraphKey gk;
+    ws::GraphKey gk;
     fill_graph_key(c, gk);
 
     static const bool host_prof = getenv_is("TDA_HOST_PROF", "1");
@@ -1101,8 +961,8 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
     }
     if (int rc = launch_or_capture(c, gk)) return rc;
     if (a.want_dist) {
-        HIPC(hipMemcpyAsync(w.hdist, c.dist, sizeof(float) * L * n * n, hipMemcpyDeviceToHost, s));
-        if (p.want64) HIPC(hipMemcpyAsync(w.hdist + sizeof(float) * L * n * n, c.B + p.o_d64, sizeof(double) * L * n * n, hipMemcpyDeviceToHost, s));
+        HIPC(hipMemcpyAsync(w.hdist.p, c.dist, sizeof(float) * L * n * n, hipMemcpyDeviceToHost, s));
+        if (p.want64) HIPC(hipMemcpyAsync(w.hdist.p + sizeof(float) * L * n * n, c.B + p.o_d64, sizeof(double) * L * n * n, hipMemcpyDeviceToHost, s));
     }
     hp.h1 = HostProf::clk::now();
     // (an event sync or a busy-polled end event measured the same for one call at a time, r02; and
@@ -1125,7 +985,7 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
     remember_retry(c);
     std::vector<int> cap_miss;  // layers whose capped reduction missed (ERR_CAP_MISS): re-run below without caps
     for (int l = 0; l < L; ++l)
-        if (w.hstats[l].err & ERR_CAP_MISS) cap_miss.push_back(l);
+        if (w.hstats.p[l].err & ERR_CAP_MISS) cap_miss.push_back(l);
     ResultImpl* R = build_result(c);
     if (host_prof) hp.add(R->pub.device_ms);
     if (!cap_miss.empty()) {

@@ -356,8 +356,8 @@ int enqueue_side(Call& c) {
     HIPC(hipEventRecord(w.evh, s4));
     if (c.nls) {  // silhouette scores on the same distance matrices (sklearn semantics), after the H0 join
         const size_t lds = (size_t)c.sil_K * kSilT * 8 + (size_t)n * 4;
-        hipLaunchKernelGGL(k_silhouette, dim3(L, c.nls), dim3(kSilT), lds, s4, dist, n, (const int32_t*)w.hsil_dev, c.sil_K,
-                           (double*)(w.hsil_dev + c.sil_out_off));
+        hipLaunchKernelGGL(k_silhouette, dim3(L, c.nls), dim3(kSilT), lds, s4, dist, n, (const int32_t*)w.hsil.dev, c.sil_K,
+                           (double*)(w.hsil.dev + c.sil_out_off));
         HIPC(hipGetLastError());
         if (int rc = c.tm4.mark("k_silhouette")) return rc;
     }
@@ -369,7 +369,7 @@ int enqueue_side(Call& c) {
         const bool tn_s2 = !p.dense && p.maxdim == 0;
         const int pw2 = (int)next_pow2((uint64_t)std::max(n, 64));
         hipLaunchKernelGGL(k_twonn, dim3(L), dim3(kTnT), (size_t)pw2 * 4, tn_s2 ? s2 : s4, dist, n, a.twonn_discard, a.twonn_eps, pw2,
-                           w.htn_dev);
+                           w.htn.dev);
         HIPC(hipGetLastError());
         if (int rc = (tn_s2 ? c.tm2 : c.tm4).mark("k_twonn")) return rc;
     }
@@ -650,7 +650,7 @@ void launch_k_emit(Call& c) {
     const Plan& p = c.p;
     Workspace& w = c.w;
     hipLaunchKernelGGL(k_emit, dim3(c.L), dim3(1024), kEmitLds, c.s, c.stats, c.L, p.maxdim, c.ps, (uint64_t*)(c.B + p.o_fk),
-                       (uint32_t*)(c.B + p.o_fv), p.sstride, w.houtoff_dev, w.hout_dev, (uint64_t)w.hout_cap, w.hstats_dev);
+                       (uint32_t*)(c.B + p.o_fv), p.sstride, w.houtoff.dev, w.hout.dev, (uint64_t)w.hout.cap, w.hstats.dev);
 }
 
 // ---- emission order, straight into host-mapped memory

@@ -40,32 +40,32 @@ void print_profile_dense(Call& c) {
     int arg = 0;
     uint64_t p1max = 0;
     for (int l = 0; l < L; ++l) {
-        if (w.hstats[l].prof[0][0] > w.hstats[arg].prof[0][0]) arg = l;
-        p1max = std::max<uint64_t>(p1max, w.hstats[l].prof[1][0]);
+        if (w.hstats.p[l].prof[0][0] > w.hstats.p[arg].prof[0][0]) arg = l;
+        p1max = std::max<uint64_t>(p1max, w.hstats.p[l].prof[1][0]);
     }
-    const uint64_t* q = w.hstats[arg].prof[0];
+    const uint64_t* q = w.hstats.p[arg].prof[0];
     fprintf(stderr, "[tda-prof] dense H1 slowest layer %d adds %lld: total %llu pivot %llu (calls %llu ties %llu) cob_app %llu add_owner %llu new_pair %llu cycles; H2 phase-1 slowest wave %llu cycles\n",
-            arg, (long long)w.hstats[arg].n_adds[1], (unsigned long long)q[0], (unsigned long long)q[1], (unsigned long long)q[7],
+            arg, (long long)w.hstats.p[arg].n_adds[1], (unsigned long long)q[0], (unsigned long long)q[1], (unsigned long long)q[7],
             (unsigned long long)q[2], (unsigned long long)q[3], (unsigned long long)q[4], (unsigned long long)q[5],
             (unsigned long long)p1max);
     uint64_t sc = 0, cb = 0, tt = 0, ad = 0, mx = 0, mxa = 0;
     for (int l = 0; l < L; ++l) {
-        sc += w.hstats[l].prof[1][4];
-        cb += w.hstats[l].prof[1][5];
-        tt += w.hstats[l].prof[1][6];
-        ad += w.hstats[l].prof[1][7];
-        if (w.hstats[l].prof[1][2] > mx) {
-            mx = w.hstats[l].prof[1][2];
-            mxa = w.hstats[l].prof[1][3] & 0xFFFF;
+        sc += w.hstats.p[l].prof[1][4];
+        cb += w.hstats.p[l].prof[1][5];
+        tt += w.hstats.p[l].prof[1][6];
+        ad += w.hstats.p[l].prof[1][7];
+        if (w.hstats.p[l].prof[1][2] > mx) {
+            mx = w.hstats.p[l].prof[1][2];
+            mxa = w.hstats.p[l].prof[1][3] & 0xFFFF;
         }
     }
     {
-        const uint64_t* e = w.hstats[0].prof[4];
+        const uint64_t* e = w.hstats.p[0].prof[4];
         fprintf(stderr, "[tda-prof] k_prep_edges layer 0 (us from block entry): sort block thresh %.2f staged %.2f sorted %.2f end %.2f; mask blocks (max) thresh %.2f staged %.2f end %.2f\n",
                 e[0] * 0.01, e[1] * 0.01, e[2] * 0.01, e[3] * 0.01, e[4] * 0.01, e[5] * 0.01, e[6] * 0.01);
     }
     {
-        const uint64_t* h = w.hstats[0].prof[3];
+        const uint64_t* h = w.hstats.p[0].prof[3];
         fprintf(stderr, "[tda-prof] k_h0_wave layer 0 (cycles from entry): thresh %llu prim %llu sort %llu unionfind %llu end %llu; chain staging (slowest layer) %llu\n",
                 (unsigned long long)h[1], (unsigned long long)h[2], (unsigned long long)h[3], (unsigned long long)h[4],
                 (unsigned long long)h[5], (unsigned long long)q[6]);
@@ -102,21 +102,21 @@ int print_profile_par(Call& c) {
                     (unsigned long long)(d[i * 4 + 3] & ~(1ull << 63)), (d[i * 4 + 3] >> 63) ? " (resumed)" : "");
         }
     }
-    const uint64_t* q = w.hstats[0].prof[2];
+    const uint64_t* q = w.hstats.p[0].prof[2];
     fprintf(stderr, "[tda-prof] k_reduce_par longest column: %llu steps, %llu cycles: front_min %llu, pivot+rows %llu, apparent adds %llu, refills %llu (%llu), owner path %llu; avg front log %llu, compactions %llu, spills %llu\n",
             (unsigned long long)q[6], (unsigned long long)q[0], (unsigned long long)q[1], (unsigned long long)q[2], (unsigned long long)q[3],
             (unsigned long long)q[4], (unsigned long long)((q[7] >> 16) & 0xFFFF), (unsigned long long)q[5], (unsigned long long)(q[7] & 0xFFFF),
             (unsigned long long)((q[7] >> 32) & 0xFFFF), (unsigned long long)(q[7] >> 48));
-    const uint64_t* u = w.hstats[0].prof[3];
+    const uint64_t* u = w.hstats.p[0].prof[3];
     fprintf(stderr, "[tda-prof]   inside adds: keys %llu, capacity %llu, front toggles %llu, bucket appends %llu cycles; %llu record adds (%llu keys); refills moved %llu keys; wave 0 toggled %llu front / %llu back keys\n",
             (unsigned long long)u[0], (unsigned long long)u[3], (unsigned long long)u[1], (unsigned long long)u[2],
             (unsigned long long)u[4], (unsigned long long)u[5], (unsigned long long)u[6], (unsigned long long)(u[7] >> 32),
             (unsigned long long)(u[7] & 0xFFFFFFFFull));
-    const uint64_t* v = w.hstats[0].prof[4];
+    const uint64_t* v = w.hstats.p[0].prof[4];
     fprintf(stderr, "[tda-prof]   record adds: room %llu, col_add %llu cycles, keys front %llu / all %llu; refill pass 3 %llu cycles; %llu saves (%llu keys) %llu cycles\n",
             (unsigned long long)v[0], (unsigned long long)v[1], (unsigned long long)v[2], (unsigned long long)v[3], (unsigned long long)v[5],
             (unsigned long long)v[6], (unsigned long long)v[7], (unsigned long long)v[4]);
-    const uint64_t* y = w.hstats[0].prof[1];
+    const uint64_t* y = w.hstats.p[0].prof[1];
     fprintf(stderr, "[tda-prof]   refill phases: search %llu, loads+min %llu, histogram %llu, level choice %llu, toggles %llu, appends %llu, compactions %llu cycles; %llu keys kept in front\n",
             (unsigned long long)y[0], (unsigned long long)y[1], (unsigned long long)y[2], (unsigned long long)y[3],
             (unsigned long long)y[4], (unsigned long long)y[5], (unsigned long long)y[6], (unsigned long long)y[7]);
@@ -129,7 +129,7 @@ int print_profile(Call& c) {
     const int n = c.n, L = c.L;
     if (p.dense && !p.par) print_profile_dense(c);
     if (n > kSmallN) {
-        const uint64_t* h = w.hstats[0].prof[0];
+        const uint64_t* h = w.hstats.p[0].prof[0];
         fprintf(stderr, "[tda-prof] k_h0 layer 0 (cycles from entry): staged %llu, thresh+edges %llu, forest %llu, sort %llu, end %llu\n",
                 (unsigned long long)h[0], (unsigned long long)h[1], (unsigned long long)h[2], (unsigned long long)h[3],
                 (unsigned long long)h[4]);
@@ -138,22 +138,22 @@ int print_profile(Call& c) {
         if (int rc = print_profile_par(c)) return rc;
     if (p.big && !p.par)
         for (int d = 1; d <= p.maxdim; ++d) {
-            const uint64_t* q = w.hstats[0].prof[d];
+            const uint64_t* q = w.hstats.p[0].prof[d];
             fprintf(stderr, "[tda-prof] big dim %d layer 0: cob0 %llu pop %llu owner_add %llu app_add %llu store %llu reset %llu total %llu cycles; owner adds %llu entries %llu, all adds %lld\n",
                     d, (unsigned long long)q[0], (unsigned long long)q[1], (unsigned long long)q[2], (unsigned long long)q[3],
                     (unsigned long long)q[4], (unsigned long long)q[5], (unsigned long long)q[7], (unsigned long long)(q[6] >> 40),
-                    (unsigned long long)(q[6] & ((1ull << 40) - 1)), (long long)w.hstats[0].n_adds[d]);
+                    (unsigned long long)(q[6] & ((1ull << 40) - 1)), (long long)w.hstats.p[0].n_adds[d]);
         }
     for (int d = 1; d <= p.maxdim; ++d) {
         uint64_t mx[8] = {0};
         int arg = 0;
         for (int l = 0; l < L; ++l)
-            if (w.hstats[l].prof[d][7] > mx[7]) {
+            if (w.hstats.p[l].prof[d][7] > mx[7]) {
                 arg = l;
-                for (int i = 0; i < 8; ++i) mx[i] = w.hstats[l].prof[d][i];
+                for (int i = 0; i < 8; ++i) mx[i] = w.hstats.p[l].prof[d][i];
             }
         fprintf(stderr, "[tda-prof] dim %d slowest layer %d adds %lld: scan %llu lookup %llu dec+facet %llu cob_app %llu toggles %llu reset %llu compact %llu total %llu cycles\n",
-                d, arg, (long long)w.hstats[arg].n_adds[d], (unsigned long long)mx[0], (unsigned long long)mx[1], (unsigned long long)mx[2],
+                d, arg, (long long)w.hstats.p[arg].n_adds[d], (unsigned long long)mx[0], (unsigned long long)mx[1], (unsigned long long)mx[2],
                 (unsigned long long)mx[3], (unsigned long long)mx[4], (unsigned long long)mx[5], (unsigned long long)mx[6], (unsigned long long)mx[7]);
     }
     return 0;

@@ -65,7 +65,7 @@ extern "C" int tda_umap_batch(const tda_umap_args* a) {
                  o_eps = cv.take(L * ecap * 8), o_nxt = cv.take(L * ecap * 8), o_nxn = cv.take(L * ecap * 8), o_deg = cv.take(L * N * 4),
                  o_emb = cv.take(L * N * c * 4);
     if (int rc = aux_reserve(w, cv.o)) return rc;
-    char* B = w.buf;
+    char* B = w.buf.p;
     hipStream_t s = w.stream;
     if (a->x_on_device)
         if (int rc = aux_after_caller(w, a->stream)) return rc;
@@ -171,7 +171,7 @@ extern "C" int tda_umap_transform(const tda_umap_transform_args* a) {
                  o_eps = cv.take(L * ecap * 8), o_nxt = cv.take(L * ecap * 8), o_nxn = cv.take(L * ecap * 8),
                  o_temb = cv.take(N * c * 4), o_emb = cv.take(L * M * c * 4);
     if (int rc = aux_reserve(w, cv.o)) return rc;
-    char* B = w.buf;
+    char* B = w.buf.p;
     const void* xt = a->x_train;
     const void* y = a->y;
     if (!a->x_on_device) {

@@ -766,7 +766,7 @@ def test_slot_growth_while_another_slot_captures(gpu, oracle):
     """slot 7's call needs a much larger workspace (N = 1024:
     hipFree + hipMalloc of its device buffers) exactly while slot 6's first
     N = 48 call captures and instantiates its graph.  Workspace (re)allocation
-    and graph capture share one lock (rips.hip g_capture_mu), so both results
+    and graph capture share one lock (ws_life.h g_capture_mu), so both results
     equal the one-at-a-time results.  Run once; not a stress loop."""
     import threading
 
