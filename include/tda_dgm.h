@@ -1,6 +1,6 @@
 /*
  * tda_dgm.h -- distances between persistence diagrams, their vectorisations
- * (landscapes, images) and the heat kernel, on the MI355X (gfx950).
+ * (landscapes, images, persistence curves) and the heat kernel, on the MI355X (gfx950).
  * Part of libtda_rips.so: error codes, tda_last_error() and tda_device_ok()
  * are those of tda_rips.h.  Added to ABI 8 (new symbols only; no existing
  * struct changed).
@@ -249,6 +249,43 @@
  * TDA_E_UNSUPPORTED for a diagram beyond the point limit (whether a pair names it or not:
  * every diagram has a self) and for too many parts.  All argument errors arrive before any
  * device work.
+ *
+ * tda_persistence_curve: persistence curves (Chung and Lawson 2019) of S diagrams on a grid, in
+ * one call: the Betti curve, the lifespan curve, the entropy summary function (Atienza,
+ * Gonzalez-Diaz, Soriano-Trigueros 2020), the silhouette (Chazal et al. 2014) and any other sum of
+ * one term per point.  For a diagram A, a coefficient c_p per row and a grid value t:
+ *     K_p(t) = 1 where b_p <= t and t < d_p, else 0                 TDA_PC_INDICATOR
+ *     K_p(t) = max(0, min(t - b_p, d_p - t))                       TDA_PC_TENT (the landscape's tent)
+ *     acc    = +0.0; for p in row order: if K_p(t) > 0: acc = acc + (c_p * K_p(t))
+ *     values[s][g] = acc                                           at t = grid[g]
+ * Everything is float64.  The tent is one rounded subtraction, the product is rounded and the sum
+ * is rounded (no fused multiply-add); a point outside its support adds nothing, not even a zero.
+ * With coef == NULL every c_p is 1 and the term is K_p(t) itself (no product).  So every value
+ * equals a numpy restatement bit for bit.
+ *
+ * Rows kept: those with a finite b and a finite d.  The indicator with TDA_PC_KEEP_ESSENTIAL also
+ * keeps the rows with a finite b and d = +inf (a Betti number counts the essential classes, and
+ * t < +inf needs no arithmetic); the flag with the tent is TDA_E_INVALID.  Every other row is
+ * dropped with its coefficient.
+ *
+ * With TDA_PC_NORMALIZE, values[s][g] = acc / W_s: W_s the sum of the kept c_p in row order from
+ * +0.0 (the number n of kept rows when coef is NULL), one rounded division; a quotient that is a
+ * zero of either sign is +0.0, and a diagram with W_s == 0 or without a kept row is +0.0
+ * everywhere.  No value is -0.0, with or without the flag.
+ *
+ * Promised bit for bit: a value depends on its diagram, its grid value, kernel and flags alone --
+ * not on the other diagrams, the diagram's place in the call, the grid value's place in the grid,
+ * a size class or the launch shape -- and is the same from run to run.  grid holds G finite values
+ * in any order.
+ *
+ * Limits: at most TDA_VEC_MAX_POINTS kept rows per diagram, G <= TDA_PL_MAX_STEPS, S * G <=
+ * TDA_VEC_MAX_OUT and S <= TDA_SW_MAX_WORK, else TDA_E_UNSUPPORTED.  The checks, in this order:
+ * args NULL, reserved != 0, an unknown kernel, an unknown bit of flags, TDA_PC_KEEP_ESSENTIAL with
+ * the tent, G < 1, grid NULL (TDA_E_INVALID), G > TDA_PL_MAX_STEPS (TDA_E_UNSUPPORTED), a
+ * non-finite grid value, S < 0, offsets NULL, bad offsets, points NULL (TDA_E_INVALID), too many
+ * diagrams (TDA_E_UNSUPPORTED), a non-finite coefficient on a kept row (TDA_E_INVALID), a diagram
+ * beyond the point limit, S * G beyond the output limit (TDA_E_UNSUPPORTED).  All argument errors
+ * arrive before any device work.
  */
 #ifndef TDA_DGM_H
 #define TDA_DGM_H
@@ -377,6 +414,34 @@ typedef struct tda_pi_result {
 
 int tda_persistence_image(const tda_pi_args *args, tda_pi_result **out);
 void tda_pi_free(tda_pi_result *r);
+
+#define TDA_PC_INDICATOR 0      /* kernel: 1 on [b, d)                              */
+#define TDA_PC_TENT 1           /* kernel: max(0, min(t - b, d - t))                */
+#define TDA_PC_NORMALIZE 1      /* flags: divide by the sum of the coefficients     */
+#define TDA_PC_KEEP_ESSENTIAL 2 /* flags: keep (finite b, +inf) rows; indicator only */
+
+typedef struct tda_pc_args {
+    const double *points;   /* host (total, 2) f64 (birth, death); see "Rows kept"                    */
+    const int64_t *offsets; /* host [S + 1] non-decreasing row boundaries, offsets[0] = 0             */
+    int64_t S;              /* diagrams                                                               */
+    const double *coef;     /* host [total] f64, one per row of points, or NULL: every c_p = 1        */
+    const double *grid;     /* host [G] finite grid values, any order                                 */
+    int32_t G;              /* 1 .. TDA_PL_MAX_STEPS                                                  */
+    int32_t kernel;         /* TDA_PC_INDICATOR or TDA_PC_TENT                                        */
+    int32_t flags;          /* 0 or TDA_PC_NORMALIZE | TDA_PC_KEEP_ESSENTIAL                          */
+    int32_t device;         /* HIP device ordinal                                                     */
+    int32_t reserved;       /* must be 0                                                              */
+} tda_pc_args;
+
+typedef struct tda_pc_result {
+    int64_t S;            /* diagrams                                              */
+    int64_t F;            /* values per diagram, G                                 */
+    const double *values; /* host [S][G]                                           */
+    double device_ms;     /* device time of the call (HIP events, copies included) */
+} tda_pc_result;
+
+int tda_persistence_curve(const tda_pc_args *args, tda_pc_result **out);
+void tda_pc_free(tda_pc_result *r);
 
 #define TDA_HK_MAX_POINTS 4096 /* finite points of one diagram   */
 #define TDA_HK_EXP_ULP 3       /* E of the accuracy bound C(n1, n2) */

@@ -384,6 +384,36 @@ TDA_PI_MAX_PIXELS = 256  # per axis
 TDA_PI_ERF_ULP = 16  # E of the image's accuracy bound C(n) = 2 E + 9 + n
 
 
+class PcArgs(ctypes.Structure):  # include/tda_dgm.h tda_pc_args
+    _fields_ = [
+        ("points", ctypes.c_void_p),
+        ("offsets", ctypes.c_void_p),
+        ("S", ctypes.c_int64),
+        ("coef", ctypes.c_void_p),
+        ("grid", ctypes.c_void_p),
+        ("G", ctypes.c_int32),
+        ("kernel", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PcResult(ctypes.Structure):  # include/tda_dgm.h tda_pc_result
+    _fields_ = [
+        ("S", ctypes.c_int64),
+        ("F", ctypes.c_int64),
+        ("values", ctypes.POINTER(ctypes.c_double)),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
+TDA_PC_INDICATOR = 0  # kernel: 1 on [b, d)
+TDA_PC_TENT = 1  # kernel: max(0, min(t - b, d - t))
+TDA_PC_NORMALIZE = 1  # flags
+TDA_PC_KEEP_ESSENTIAL = 2  # flags: indicator only
+
+
 class HkArgs(ctypes.Structure):  # include/tda_dgm.h tda_hk_args
     _fields_ = [
         ("points", ctypes.c_void_p),
@@ -453,6 +483,7 @@ DGM_ENTRIES = {
     "pl": ("tda_landscape", "tda_pl_free", PlArgs, PlResult),
     "pi": ("tda_persistence_image", "tda_pi_free", PiArgs, PiResult),
     "hk": ("tda_heat_kernel", "tda_hk_free", HkArgs, HkResult),
+    "pc": ("tda_persistence_curve", "tda_pc_free", PcArgs, PcResult),
 }
 # their symbols, one tuple per addition to the header
 DGM_EXPORTS = DGM_ENTRIES["sw"][:2]
@@ -460,6 +491,7 @@ BOTTLENECK_EXPORTS = DGM_ENTRIES["bn"][:2]
 WASSERSTEIN_EXPORTS = DGM_ENTRIES["ws"][:2]
 VECTOR_EXPORTS = DGM_ENTRIES["pl"][:2] + DGM_ENTRIES["pi"][:2]
 HEAT_EXPORTS = DGM_ENTRIES["hk"][:2]
+CURVE_EXPORTS = DGM_ENTRIES["pc"][:2]
 
 _lib = None
 

@@ -1,9 +1,9 @@
-// dgm_plan.h -- the host plans of the six entries of include/tda_dgm.h, one per entry: sw_plan, bn_plan
+// dgm_plan.h -- the host plans of the seven entries of include/tda_dgm.h, one per entry: sw_plan, bn_plan
 // and ws_plan (PairPlan: the layout checks, the finite points and the pair list, the pairs sorted into size
 // classes and, for tda_wasserstein, oriented canonically), hk_plan (HkPlan: the work list of
-// tda_heat_kernel) and pl_plan / pi_plan (VecPlan: per diagram, at the end), each with the size classes
+// tda_heat_kernel) and pl_plan / pi_plan / pc_plan (VecPlan: per diagram, at the end), each with the size classes
 // of its launches.  Plain C++, no HIP: a plan returns an error code and leaves its message in `msg`
-// (tests/dgm_plan_main.cpp, ws_plan_main.cpp, hk_plan_main.cpp and vec_plan_main.cpp run them with a
+// (tests/dgm_plan_main.cpp, ws_plan_main.cpp, hk_plan_main.cpp, vec_plan_main.cpp and pc_plan_main.cpp run them with a
 // host compiler alone).  The checks of a plan run in the order its entry has always made them.
 #pragma once
 #include <algorithm>
@@ -300,16 +300,26 @@ struct VecPlan {
     int64_t S = 0;
 };
 
-// the layout checks, the finite points and the classes; `what` names the entry in the messages
-inline int vec_gather(const double* points, const int64_t* offsets, int64_t S, const char* what, VecPlan& pl, std::string& msg) {
+// the layout checks of a per-diagram entry; `what` names the entry in the messages
+inline int vec_check(const double* points, const int64_t* offsets, int64_t S, const char* what, std::string& msg) {
     if (S < 0) return msg = "S must be >= 0", TDA_E_INVALID;
     if (!offsets) return msg = "offsets is NULL", TDA_E_INVALID;
-    if (int rc = dgm_check_layout(points, offsets, S, nullptr, 0, what, msg)) return rc;
-    pl.S = S;
-    dgm_gather_points(points, offsets, S, pl.pts, pl.off);
-    if (!dgm_sort_classes(S, [&](int64_t s) { return pl.off[s + 1] - pl.off[s]; }, kVecClassN, pl.order, pl.cls_cnt, pl.cls_n))
+    return dgm_check_layout(points, offsets, S, nullptr, 0, what, msg);
+}
+
+// the gathered diagrams (pl.off) sorted into the size classes
+inline int vec_classify(const char* what, VecPlan& pl, std::string& msg) {
+    if (!dgm_sort_classes(pl.S, [&](int64_t s) { return pl.off[s + 1] - pl.off[s]; }, kVecClassN, pl.order, pl.cls_cnt, pl.cls_n))
         return msg = std::string(what) + ": a diagram with more than 4096 finite points is not supported", TDA_E_UNSUPPORTED;
     return 0;
+}
+
+// the layout checks, the finite points and the classes
+inline int vec_gather(const double* points, const int64_t* offsets, int64_t S, const char* what, VecPlan& pl, std::string& msg) {
+    if (int rc = vec_check(points, offsets, S, what, msg)) return rc;
+    pl.S = S;
+    dgm_gather_points(points, offsets, S, pl.pts, pl.off);
+    return vec_classify(what, pl, msg);
 }
 
 inline int pl_plan(const tda_pl_args* a, VecPlan& pl, std::string& msg) {
@@ -362,6 +372,60 @@ inline int pi_plan(const tda_pi_args* a, VecPlan& pl, std::string& msg) {
     if (a->S * ((int64_t)a->W * a->H) > TDA_VEC_MAX_OUT)
         return bad(TDA_E_UNSUPPORTED, "persistence image: S * W * H > 2^24 values in one call is not supported (split the diagrams)");
     pi_weights(pl, a->weight_power);
+    return 0;
+}
+
+// ---------------------------------------------------------------- persistence curves (tda_persistence_curve)
+// A VecPlan whose rows are the kept rows (with TDA_PC_KEEP_ESSENTIAL also those with d = +inf), wgt
+// their coefficients (empty for coef == NULL), and W the divisor of every diagram.  The launches
+// (pc_host.h): class 0 of the plan (n <= kPcPackN) packed, one diagram per wave; the classes
+// above it together, one diagram per workgroup with its rows in chunks of kPcChunk.
+
+constexpr int kPcPackN = kVecClassN[0];  // a packed diagram's rows at most: one row per lane when staged
+constexpr int kPcChunk = 1024;           // rows of a chunked workgroup's LDS
+
+struct PcPlan {
+    VecPlan v;
+    std::vector<double> W;  // [S]: the row-order sum of the kept coefficients, or the number of kept rows
+};
+
+inline int pc_plan(const tda_pc_args* a, PcPlan& pp, std::string& msg) {
+    auto bad = [&](int code, const char* m) { return msg = m, code; };
+    if (!a) return bad(TDA_E_INVALID, "args is NULL");
+    if (a->reserved != 0) return bad(TDA_E_INVALID, "reserved must be 0");
+    if (a->kernel != TDA_PC_INDICATOR && a->kernel != TDA_PC_TENT) return bad(TDA_E_INVALID, "kernel must be TDA_PC_INDICATOR or TDA_PC_TENT");
+    if (a->flags & ~(TDA_PC_NORMALIZE | TDA_PC_KEEP_ESSENTIAL)) return bad(TDA_E_INVALID, "flags holds an unknown bit");
+    const bool essential = a->flags & TDA_PC_KEEP_ESSENTIAL;
+    if (essential && a->kernel == TDA_PC_TENT) return bad(TDA_E_INVALID, "TDA_PC_KEEP_ESSENTIAL needs the indicator kernel: a tent has no value on an essential row");
+    if (a->G < 1) return bad(TDA_E_INVALID, "G must be >= 1");
+    if (!a->grid) return bad(TDA_E_INVALID, "grid is NULL");
+    if (a->G > TDA_PL_MAX_STEPS) return bad(TDA_E_UNSUPPORTED, "persistence curve: G > 4096 grid values is not supported");
+    for (int32_t g = 0; g < a->G; ++g)
+        if (!std::isfinite(a->grid[g])) return bad(TDA_E_INVALID, "grid holds a non-finite value");
+    if (int rc = vec_check(a->points, a->offsets, a->S, "persistence curve", msg)) return rc;
+    VecPlan& pl = pp.v;
+    pl.S = a->S;
+    pl.off.assign((size_t)a->S + 1, 0);
+    pp.W.assign((size_t)a->S, 0.0);
+    for (int64_t s = 0; s < a->S; ++s) {
+        double w = 0.0;
+        for (int64_t r = a->offsets[s]; r < a->offsets[s + 1]; ++r) {
+            const double b = a->points[2 * r], d = a->points[2 * r + 1];
+            if (!std::isfinite(b) || !(std::isfinite(d) || (essential && d > 0.0 && std::isinf(d)))) continue;
+            pl.pts.push_back(b);
+            pl.pts.push_back(d);
+            if (a->coef) {
+                if (!std::isfinite(a->coef[r])) return bad(TDA_E_INVALID, "coef holds a non-finite value on a kept row");
+                pl.wgt.push_back(a->coef[r]);
+                w = w + a->coef[r];
+            }
+        }
+        pl.off[s + 1] = (int64_t)(pl.pts.size() / 2);
+        pp.W[s] = a->coef ? w : (double)(pl.off[s + 1] - pl.off[s]);
+    }
+    if (int rc = vec_classify("persistence curve", pl, msg)) return rc;
+    if (a->S * (int64_t)a->G > TDA_VEC_MAX_OUT)
+        return bad(TDA_E_UNSUPPORTED, "persistence curve: S * G > 2^24 values in one call is not supported (split the diagrams)");
     return 0;
 }
 

@@ -1199,3 +1199,5 @@ void tda_pipe_destroy(tda_pipe* pipe) { delete pipe; }
 #include "vec_host.h"
 // the heat (scale-space) kernel between persistence diagrams and its distance (include/tda_dgm.h)
 #include "hk_host.h"
+// persistence curves: Betti, lifespan, entropy, silhouette (include/tda_dgm.h)
+#include "pc_host.h"

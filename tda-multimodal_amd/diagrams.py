@@ -44,6 +44,11 @@ positive semi-definite: the one distance here that kernel PCA, an SVM or an MMD
 test can use as it is.  A double sum of exponentials, summed in an order that the
 two point counts alone decide; a diagram may hold 4096 finite points.
 
+``persistence_curves`` sums one term per point on a grid of filtration values (Chung and
+Lawson 2019): ``betti_curves``, ``lifespan_curves``, ``entropy_curves`` and
+``persistence_silhouettes`` are its named forms, the functions of the radius a layer study
+plots.  Every value equals a numpy loop over the points in row order, bit for bit.
+
 ``persistence_landscapes`` and ``persistence_images`` are the two standard
 vectorisations [upstream ``persim.landscapes``, ``persim.PersistenceImager``]:
 one fixed-length vector per diagram, linear in the number of diagrams, no
@@ -417,6 +422,21 @@ def _check_out(S: int, F: int):
         raise NotImplementedError(f"{S} diagrams of {F} values: more than 2^24 values in one call is not supported (split the diagrams)")
 
 
+def _linspace_grid(start, stop, G: int, births, deaths):
+    """``np.linspace(start, stop, G)``; an end left None is the smallest of ``births`` / the largest of ``deaths``."""
+    if (start is None and not len(births)) or (stop is None and not len(deaths)):
+        raise ValueError("no diagram holds a finite point: start and stop must be given")
+    start = float(births.min()) if start is None else float(start)
+    stop = float(deaths.max()) if stop is None else float(stop)
+    if not (np.isfinite(start) and np.isfinite(stop)):
+        raise ValueError("start and stop must be finite")
+    with np.errstate(all="ignore"):
+        grid = np.ascontiguousarray(np.linspace(start, stop, G), dtype=np.float64)
+    if not np.isfinite(grid).all():
+        raise ValueError("start and stop span more than float64 holds")
+    return grid
+
+
 def _call_pl(points, offsets, grid, K: int, device: int):
     """One tda_landscape call: (values (S, K, G), device_ms)."""
     read = lambda r: (_owned(r.values, r.S * r.F).reshape(r.S, K, len(grid)), float(r.device_ms))  # noqa: E731
@@ -442,18 +462,7 @@ def persistence_landscapes(dgms, start=None, stop=None, num_steps: int = 500, de
     G = _check_int("num_steps", num_steps, _lib.TDA_PL_MAX_STEPS)
     pts, off, S = _vec_inputs(dgms, dim)
     fin = pts[np.isfinite(pts).all(axis=1)]
-    if start is None or stop is None:
-        if not len(fin):
-            raise ValueError("no diagram holds a finite point: start and stop must be given")
-        start = float(fin[:, 0].min()) if start is None else start
-        stop = float(fin[:, 1].max()) if stop is None else stop
-    start, stop = float(start), float(stop)
-    if not (np.isfinite(start) and np.isfinite(stop)):
-        raise ValueError("start and stop must be finite")
-    with np.errstate(all="ignore"):
-        grid = np.ascontiguousarray(np.linspace(start, stop, G), dtype=np.float64)
-    if not np.isfinite(grid).all():
-        raise ValueError("start and stop span more than float64 holds")
+    grid = _linspace_grid(start, stop, G, fin[:, 0], fin[:, 1])
     _check_out(S, K * G)
     out, ms = (np.zeros((0, K, G)), 0.0) if S == 0 else _call_pl(pts, off, grid, K, device)
     res = (out,) + ((grid,) if return_grid else ()) + ((ms,) if return_time else ())
@@ -526,3 +535,195 @@ def persistence_image(dgm, birth_range, pers_range, resolution, sigma: float, we
     if isinstance(dgm, LayerResult):
         raise ValueError("dgm is an (n, 2) array (for LayerResults: persistence_images)")
     return persistence_images([dgm], birth_range, pers_range, resolution, sigma, weight_power, device=device)[0]
+
+
+# ---------------------------------------------------------------- persistence curves (tda_persistence_curve)
+_PC_KERNELS = {"indicator": _lib.TDA_PC_INDICATOR, "tent": _lib.TDA_PC_TENT}
+
+
+def _call_pc(points, offsets, coef, grid, kernel: int, flags: int, device: int):
+    """One tda_persistence_curve call: (values (S, G), device_ms)."""
+    read = lambda r: (_owned(r.values, r.S * r.F).reshape(r.S, len(grid)), float(r.device_ms))  # noqa: E731
+    return _library_call("pc", points, offsets, None, read, coef=None if coef is None else coef.ctypes.data, grid=grid.ctypes.data,
+                         G=len(grid), kernel=kernel, flags=flags, device=int(device))
+
+
+def _pc_inputs(dgms, dim: int, essential: bool):
+    """(points, offsets, kept) of a curve call: ``kept`` marks the rows the library keeps, those with a
+    finite birth and a finite death or, with ``essential``, a death of +inf.  The point limit is checked
+    and the dropped rows are reported, before any library call."""
+    pts, off = _flatten(dgms, dim)
+    b, d = pts[:, 0], pts[:, 1]
+    kept = np.isfinite(b) & (np.isfinite(d) | (d == np.inf)) if essential else np.isfinite(pts).all(axis=1)
+    c = np.concatenate([[0], np.cumsum(kept)])
+    cnt = c[off[1:]] - c[off[:-1]]
+    if len(cnt) and cnt.max() > _lib.TDA_VEC_MAX_POINTS:
+        raise NotImplementedError(f"a diagram holds {int(cnt.max())} finite points: more than {_lib.TDA_VEC_MAX_POINTS} is not supported")
+    dropped = int(len(kept) - c[-1])
+    if dropped:
+        warnings.warn(f"the diagrams hold {dropped} points with a non-finite coordinate; ignoring those points")
+    return pts, off, kept
+
+
+def _run_pc(pts, off, kept, coef, grid, kernel: str, normalize: bool, essential: bool, device: int):
+    """The call of the entries below, after their checks: (values (S, G), device_ms)."""
+    S, G = len(off) - 1, len(grid)
+    if coef is not None and not np.isfinite(coef[kept]).all():
+        raise ValueError("coef holds a non-finite value on a row with a finite (birth, death)")
+    _check_out(S, G)
+    flags = (_lib.TDA_PC_NORMALIZE if normalize else 0) | (_lib.TDA_PC_KEEP_ESSENTIAL if essential else 0)
+    return (np.zeros((0, G)), 0.0) if S == 0 else _call_pc(pts, off, coef, grid, _PC_KERNELS[kernel], flags, device)
+
+
+def persistence_curves(dgms, grid, coef=None, kernel: str = "indicator", normalize: bool = False, essential: bool = False, dim: int = 1,
+                       device: int = 0, return_time: bool = False):
+    """Persistence curves (Chung and Lawson 2019) of a list of diagrams on ``grid``, one library call:
+    the (S, G) float64 array
+
+        F_s(t) = sum over the points p of diagram s, in row order, of coef[s][p] * K(b_p, d_p, t),
+
+    K the indicator of ``b <= t < d`` (``kernel="indicator"``) or the tent ``max(0, min(t - b, d - t))``
+    (``kernel="tent"``).  ``coef`` is a list of S arrays, one coefficient per row of each diagram, or
+    None for all ones; with ``normalize`` every curve is divided by the sum of its diagram's
+    coefficients (a diagram whose sum is 0 gives zeros).  Rows with a non-finite coordinate are
+    ignored, with a warning, and their coefficients with them; with ``essential`` (indicator only) the
+    rows with a death of +inf are kept and count from their birth on.
+
+    Every value is the sum ``acc = acc + coef * K`` over the points with K > 0, from +0.0 in row order,
+    each product and each sum rounded once: a numpy loop gives the same bits, and a diagram's curve is
+    the same bits in any call that holds it.  ``grid`` holds 1 .. 4096 finite values in any order; a
+    diagram may hold 4096 kept rows.  dgms and dim are those of :func:`persistence_landscapes`; with
+    ``return_time`` also the call's device time in ms."""
+    if kernel not in _PC_KERNELS:
+        raise ValueError(f"kernel must be 'indicator' or 'tent', got {kernel!r}")
+    if essential and kernel == "tent":
+        raise ValueError("essential=True needs kernel='indicator': a tent has no value on a bar without a death")
+    grid = np.ascontiguousarray(grid, dtype=np.float64)
+    if grid.ndim != 1 or len(grid) < 1:
+        raise ValueError("grid must be a one-dimensional array of at least one value")
+    if len(grid) > _lib.TDA_PL_MAX_STEPS:
+        raise NotImplementedError(f"a grid of more than {_lib.TDA_PL_MAX_STEPS} values is not supported")
+    if not np.isfinite(grid).all():
+        raise ValueError("grid holds a non-finite value")
+    pts, off, kept = _pc_inputs(dgms, dim, bool(essential))
+    if coef is not None:
+        coef = [np.asarray(c, dtype=np.float64).reshape(-1) for c in coef]
+        if [len(c) for c in coef] != np.diff(off).tolist():
+            raise ValueError("coef must hold one array per diagram with one coefficient per row")
+        coef = np.ascontiguousarray(np.concatenate(coef) if coef else np.zeros(0), dtype=np.float64)
+    out, ms = _run_pc(pts, off, kept, coef, grid, kernel, bool(normalize), bool(essential), device)
+    return (out, ms) if return_time else out
+
+
+def _lifespan_coef(b, d):
+    return d - b
+
+
+def _entropy_coef(b, d):
+    l = d - b  # noqa: E741
+    p = l / l.sum()
+    return -p * np.log(p)
+
+
+def _named_curves(dgms, coef_of, kernel, normalize, essential, start, stop, num_steps, dim, device, return_grid, return_time,
+                  per_diagram: bool = True):
+    """The named curves: the grid of :func:`persistence_landscapes` over the kept rows, the coefficients
+    ``coef_of(births, deaths)`` of every diagram's kept rows (of all kept rows at once where the
+    formula is row by row), one :func:`persistence_curves` call."""
+    G = _check_int("num_steps", num_steps, _lib.TDA_PL_MAX_STEPS)
+    pts, off, kept = _pc_inputs(dgms, dim, essential)
+    grid = _linspace_grid(start, stop, G, pts[kept, 0], pts[kept & np.isfinite(pts[:, 1]), 1])
+    coef = None
+    if coef_of is not None:
+        coef = np.zeros(len(pts))
+        with np.errstate(all="ignore"):
+            if per_diagram:
+                for s in range(len(off) - 1):
+                    rows = off[s] + np.flatnonzero(kept[off[s]:off[s + 1]])
+                    coef[rows] = coef_of(pts[rows, 0], pts[rows, 1])
+            else:
+                coef[kept] = coef_of(pts[kept, 0], pts[kept, 1])
+    out, ms = _run_pc(pts, off, kept, coef, grid, kernel, normalize, essential, device)
+    res = (out,) + ((grid,) if return_grid else ()) + ((ms,) if return_time else ())
+    return res if len(res) > 1 else out
+
+
+def _one_curve(many, dgm, return_grid: bool, **kw):
+    if isinstance(dgm, LayerResult):
+        raise ValueError(f"dgm is an (n, 2) array (for LayerResults: {many.__name__})")
+    r = many([dgm], return_grid=return_grid, **kw)
+    return (r[0][0], r[1]) if return_grid else r[0]
+
+
+def betti_curves(dgms, start=None, stop=None, num_steps: int = 100, dim: int = 1, essential: bool = True, device: int = 0,
+                 return_grid: bool = False, return_time: bool = False):
+    """Betti curves of a list of diagrams, one library call: the (S, num_steps) float64 array of the
+    number of points with ``b <= t < d`` at t in ``np.linspace(start, stop, num_steps)`` -- the classes
+    of H_dim alive at radius t.  It is :func:`persistence_curves` with the indicator and no coefficients.
+    With ``essential`` (the default) a point with a death of +inf counts from its birth on, and is not
+    reported as non-finite.  ``start`` / ``stop`` default to the smallest birth / the largest finite
+    death of the points that count (a call without one needs both given); dgms, dim and the limits are
+    those of :func:`persistence_curves`.  With ``return_grid`` also the grid, with ``return_time`` also
+    the call's device time in ms."""
+    return _named_curves(dgms, None, "indicator", False, bool(essential), start, stop, num_steps, dim, device, return_grid, return_time)
+
+
+def betti_curve(dgm, start=None, stop=None, num_steps: int = 100, essential: bool = True, device: int = 0, return_grid: bool = False):
+    """The (num_steps,) Betti curve of one (n, 2) diagram (:func:`betti_curves`)."""
+    return _one_curve(betti_curves, dgm, return_grid, start=start, stop=stop, num_steps=num_steps, essential=essential, device=device)
+
+
+def lifespan_curves(dgms, start=None, stop=None, num_steps: int = 100, dim: int = 1, device: int = 0, return_grid: bool = False,
+                    return_time: bool = False):
+    """Lifespan curves of a list of diagrams: the (S, num_steps) float64 array of the total lifetime of
+    the points alive at t, :func:`persistence_curves` with the indicator and the coefficients
+    ``c = d - b``.  Points with a non-finite coordinate are ignored, with a warning; the grid and the
+    other arguments are those of :func:`betti_curves`."""
+    return _named_curves(dgms, _lifespan_coef, "indicator", False, False, start, stop, num_steps, dim, device, return_grid, return_time,
+                         per_diagram=False)
+
+
+def lifespan_curve(dgm, start=None, stop=None, num_steps: int = 100, device: int = 0, return_grid: bool = False):
+    """The (num_steps,) lifespan curve of one (n, 2) diagram (:func:`lifespan_curves`)."""
+    return _one_curve(lifespan_curves, dgm, return_grid, start=start, stop=stop, num_steps=num_steps, device=device)
+
+
+def entropy_curves(dgms, start=None, stop=None, num_steps: int = 100, dim: int = 1, device: int = 0, return_grid: bool = False,
+                   return_time: bool = False):
+    """Entropy summary functions (Atienza, Gonzalez-Diaz, Soriano-Trigueros 2020) of a list of
+    diagrams: the (S, num_steps) float64 array of :func:`persistence_curves` with the indicator and,
+    per diagram, over its rows with a finite (birth, death),
+
+        l = d - b,  p = l / l.sum(),  c = -p * np.log(p).
+
+    A row with d <= b has no such coefficient (ValueError).  Points with a non-finite coordinate are
+    ignored, with a warning; the grid and the other arguments are those of :func:`betti_curves`."""
+    return _named_curves(dgms, _entropy_coef, "indicator", False, False, start, stop, num_steps, dim, device, return_grid, return_time)
+
+
+def entropy_curve(dgm, start=None, stop=None, num_steps: int = 100, device: int = 0, return_grid: bool = False):
+    """The (num_steps,) entropy summary function of one (n, 2) diagram (:func:`entropy_curves`)."""
+    return _one_curve(entropy_curves, dgm, return_grid, start=start, stop=stop, num_steps=num_steps, device=device)
+
+
+def persistence_silhouettes(dgms, start=None, stop=None, num_steps: int = 100, dim: int = 1, device: int = 0, return_grid: bool = False,
+                            return_time: bool = False, power: float = 1.0):
+    """Persistence silhouettes (Chazal et al. 2014) of a list of diagrams: the (S, num_steps) float64
+    array of the weighted average of the tents ``max(0, min(t - b, d - t))``, :func:`persistence_curves`
+    with the tent, normalised, and per diagram the coefficients
+
+        c = np.power(d - b, power)
+
+    over its rows with a finite (birth, death) (a row whose coefficient is not finite, d < b under a
+    fractional power, is a ValueError).  Points with a non-finite coordinate are ignored, with a
+    warning; the grid and the other arguments are those of :func:`betti_curves`."""
+    power = float(power)
+    if not np.isfinite(power):
+        raise ValueError(f"power must be finite, got {power}")
+    return _named_curves(dgms, lambda b, d: np.power(d - b, power), "tent", True, False, start, stop, num_steps, dim, device, return_grid,
+                         return_time)
+
+
+def persistence_silhouette(dgm, start=None, stop=None, num_steps: int = 100, device: int = 0, return_grid: bool = False, power: float = 1.0):
+    """The (num_steps,) silhouette of one (n, 2) diagram (:func:`persistence_silhouettes`)."""
+    return _one_curve(persistence_silhouettes, dgm, return_grid, start=start, stop=stop, num_steps=num_steps, device=device, power=power)

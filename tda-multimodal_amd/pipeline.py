@@ -28,7 +28,8 @@ import json
 
 import numpy as np
 
-from .diagrams import bottleneck_matrix, heat_matrix, persistence_images, persistence_landscapes, sliced_wasserstein_matrix, wasserstein_matrix
+from .diagrams import (betti_curves, bottleneck_matrix, entropy_curves, heat_matrix, lifespan_curves, persistence_images, persistence_landscapes,
+                       persistence_silhouettes, sliced_wasserstein_matrix, wasserstein_matrix)
 from .ripser import ripser_batch
 
 
@@ -132,13 +133,24 @@ def layer_features(results, kind: str = "landscape", dim: int = 1, device: int =
     (diagrams.persistence_landscapes, F = depth * num_steps; pass ``start`` and ``stop``
     to put every sweep on the same grid) or "image" (diagrams.persistence_images,
     F = nb * npers; ``birth_range``, ``pers_range``, ``resolution`` and ``sigma`` are
-    required).  ``kw`` goes to that function; each layer's array is flattened row-major."""
+    required), or one of the curves over the radius, F = num_steps: "betti"
+    (diagrams.betti_curves), "silhouette" (diagrams.persistence_silhouettes), "lifespan"
+    (diagrams.lifespan_curves) or "entropy" (diagrams.entropy_curves).  ``kw`` goes to that
+    function; each layer's array is flattened row-major."""
     if kind == "landscape":
         out = persistence_landscapes(results, dim=dim, device=device, **kw)
     elif kind == "image":
         out = persistence_images(results, dim=dim, device=device, **kw)
+    elif kind == "betti":
+        out = betti_curves(results, dim=dim, device=device, **kw)
+    elif kind == "silhouette":
+        out = persistence_silhouettes(results, dim=dim, device=device, **kw)
+    elif kind == "lifespan":
+        out = lifespan_curves(results, dim=dim, device=device, **kw)
+    elif kind == "entropy":
+        out = entropy_curves(results, dim=dim, device=device, **kw)
     else:
-        raise ValueError(f"kind must be 'landscape' or 'image', got {kind!r}")
+        raise ValueError(f"kind must be 'landscape', 'image', 'betti', 'silhouette', 'lifespan' or 'entropy', got {kind!r}")
     if isinstance(out, tuple):
         raise ValueError("layer_features returns the matrix alone: no return_grid / return_time")
     return out.reshape(len(out), -1)
