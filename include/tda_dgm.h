@@ -1,6 +1,7 @@
 /*
  * tda_dgm.h -- distances between persistence diagrams, their vectorisations
- * (landscapes, images, persistence curves) and the heat kernel, on the MI355X (gfx950).
+ * (landscapes, images, persistence curves), the heat kernel and the persistence Fisher
+ * distance, on the MI355X (gfx950).
  * Part of libtda_rips.so: error codes, tda_last_error() and tda_device_ok()
  * are those of tda_rips.h.  Added to ABI 8 (new symbols only; no existing
  * struct changed).
@@ -250,6 +251,121 @@
  * every diagram has a self) and for too many parts.  All argument errors arrive before any
  * device work.
  *
+ * tda_persistence_fisher: the persistence Fisher distance (Le and Yamada 2018; gudhi's
+ * PersistenceFisherDistance / PersistenceFisherKernel [upstream]) of P pairs out of S diagrams
+ * in one call.  Both diagrams of a pair are smoothed into densities on a common support, and
+ * the distance is the Fisher information (geodesic) distance between the two densities on the
+ * sphere.  For diagrams F (n1 rows) and G (n2 rows), after dropping every row with a
+ * non-finite coordinate, and sigma > 0:
+ *     c2        = 1 / (2 sigma sigma)       host: one rounded product, an exact doubling, one rounded division
+ *     pi(b, d)  = (m, m), m = (b + d) * 0.5      one rounded addition, the halving exact
+ *     U         = F_0 .. F_{n1-1}, pi(G_0) .. pi(G_{n2-1})        M = n1 + n2 source points
+ *     V         = G_0 .. G_{n2-1}, pi(F_0) .. pi(F_{n1-1})
+ *     Z         = U then V                                         2 M evaluation points
+ *     r2(z, w)  = (z.b - w.b)^2 + (z.d - w.d)^2    two rounded subtractions, two rounded products, one rounded addition
+ *     e(z, w)   = +0.0 if -c2 r2 < -TDA_PF_CUT (= -708), else exp(-c2 r2)     -c2 r2 one rounded product
+ *     rhoU(z)   = sum over w in U of e(z, w);   rhoV(z) likewise over V
+ *     a = sum_z rhoU(z);   b = sum_z rhoV(z);   h = sum_z sqrt(rhoU(z) * rhoV(z))
+ *     affinity  = min(1, h / sqrt(a * b))          host, this order
+ *     fisher    = arccos(affinity)                 host (libm)
+ * Everything is float64 and nothing is contracted to a fused multiply-add.  The product
+ * rhoU(z) * rhoV(z) is rounded once and its square root is the correctly rounded one: the
+ * device's __dsqrt_rn (IEEE round to nearest even).  exp(-708) = 3.3e-308 is a normal number,
+ * so the cut keeps every term either +0.0 or normal.  The Gaussian's constant
+ * 1 / (sigma sqrt(2 pi)) of the upstream formula cancels in the normalisation and is not
+ * computed.  The kernel exp(-fisher / bandwidth) is formed by the caller.  Two empty diagrams
+ * are at distance +0.0 (a = b = h = +0.0); one empty diagram is an ordinary case (U = F,
+ * V = pi(F)).  The values are bounded by pi / 2.
+ *
+ * The result, per pair: a, b, h and dist = fisher, formed on the host from the three sums.
+ * Every pair is evaluated in one canonical orientation (that of tda_heat_kernel: the diagram
+ * with more finite points is F and, at equal counts, the one whose point array comes first
+ * lexicographically); where that exchanged the two diagrams, a and b are exchanged back, so
+ * that a belongs to the U of the pair's first diagram as the caller named it.  h and dist do
+ * not depend on the naming.
+ *
+ * The order of the sums is a function of (n1, n2) alone, in the canonical orientation, with
+ * L = TDA_PF_LANES = 64:
+ *     rhoU(z), rhoV(z) = from +0.0, over the sources w = U_0 .. U_{M-1} (V_0 .. V_{M-1}) in that
+ *                        order, one rounded addition per source (a term cut to +0.0 is added
+ *                        like any other);
+ *     part[k]          = for each of a, b and h: the values of z = 64 k .. 64 k + 63 (a z beyond
+ *                        2 M counts +0.0), added pairwise over the lane index l = z - 64 k:
+ *                        lanes l and l ^ 1, then l ^ 2, l ^ 4, l ^ 8, l ^ 16, l ^ 32;
+ *     a, b, h          = the ceil(2 M / 64) <= 64 parts, part k in lane k (a lane without a part
+ *                        counts +0.0), added pairwise in the same way
+ * whatever the launch shape and whatever else the call holds.  The sources are staged
+ * TDA_PF_CHUNK = 128 of U and of V at a time; the chunk does not enter the order.
+ *
+ * What is promised, with u = 2^-53:
+ *   1. bit for bit, symmetry and identity: fisher(F, G) == fisher(G, F), h likewise, and
+ *      a(F, G) == b(G, F); fisher(F, F) is exactly +0.0 for two diagrams with the same finite
+ *      rows, named by one index or by two.  Why: with F = G the sequences U and V hold the
+ *      same bits in the same order, so rhoU(z) == rhoV(z) =: x at every z, with x in [1, 2 M]
+ *      (the term e(z, z) is exp(-0.0) = 1).  For a binary format and a correctly rounded
+ *      square root, sqrt(fl(x x)) == x when nothing over- or underflows, so every h term is the
+ *      a term and the b term, the three sums run in one order, and h == a == b.  On the host
+ *      sqrt(fl(a a)) == a for the same reason, the quotient is 1 and arccos(1) is +0.0;
+ *   2. bit for bit, independence of the call: a pair's a, b, h and dist are the same alone,
+ *      among other pairs of any sizes, at any position in the pair list, with or without an
+ *      explicit `pairs`, and from run to run;
+ *   3. accuracy: |affinity - exact| <= B(n1, n2), the exact value that of the formulas above
+ *      (the cut included) on the float64 inputs and c2, and
+ *          T         = 6 TDA_PF_CUT + 2 E + 2 = 4256,       E = TDA_PF_EXP_ULP = 3,
+ *          R(n1, n2) = T + (n1 + n2),
+ *          B(n1, n2) = (2 R(n1, n2) + 30) u + 3 (n1 + n2) 2^-510.
+ *      Derivation (first order in u; every step rounds up, which covers the u^2 terms):
+ *        a. the argument: each difference carries a relative error u, its square 3 u, the sum
+ *           of the two non-negative squares 4 u, the product with c2 5 u: t = -c2 r2 has a
+ *           relative error of at most 6 u.  A term that is kept has |t| <= 708, so
+ *           exp(t) moves by a factor within 1 +- 6 * 708 u;
+ *        b. the device exp is within E ulp, and an ulp is at most 2 u of the value: a kept term
+ *           is within a relative T u of the exact one (the + 2 for the second order);
+ *        c. a term whose exact argument lies within rounding of -708 may appear or vanish:
+ *           an additive error of at most exp(-708 (1 - 6 u)) <= 2^-1021 per term, M 2^-1021 per
+ *           density.  It is carried separately (step f);
+ *        d. a density is a sum of M non-negative terms in series, M - 1 additions: a relative
+ *           M u.  So rhoU and rhoV are within a relative R u of the exact ones (and step c);
+ *        e. sqrt(rhoU rhoV): one rounded product, one correctly rounded root:
+ *           (R + R + 1) / 2 + 1 <= R + 2 relative.  Every z lies in U or in V, so one of the
+ *           two densities holds the term e(z, z) = 1: the product is at least 3.3e-308 or is
+ *           +0.0, never subnormal;
+ *        f. step c under the root: at a z of U, rhoU >= 1 takes it as a relative error far below
+ *           u^2, and sqrt(rhoU (rhoV + d)) - sqrt(rhoU rhoV) <= sqrt(rhoU d) <= sqrt(2 M M 2^-1021);
+ *           over the 2 M values of z: at most 3 M^2 2^-510 added to h;
+ *        g. a, b and h are sums of non-negative values through 6 + 6 pairwise additions:
+ *           a and b within R + 12, h within R + 14 relative;
+ *        h. the host: a b rounded, its root, the quotient: the denominator within
+ *           ((R + 12) + (R + 12) + 1) / 2 + 1 <= R + 14.5, the quotient within
+ *           (R + 14) + (R + 14.5) + 1 <= 2 R + 30, relative to an exact value of at most 1
+ *           (Cauchy-Schwarz); min(1, .) moves nothing away from it.  Step f divided by
+ *           sqrt(a b) >= M: 3 M 2^-510.
+ *      E is the OpenCL conformance bound for double exp, as TDA_HK_EXP_ULP and for the same
+ *      reason.  B is not fitted to observed errors; at sigma where no argument comes near the
+ *      cut it is loose by the factor 6 * 708 of step a.  The largest share of B seen in the
+ *      tests is 2.3e-4 (one ulp of the affinity).
+ *      The distance: with A the affinity computed,
+ *          |fisher - exact| <= arccos(max(-1, A - B)) - arccos(min(1, A + B)) + 4 u
+ *      (arccos is decreasing, the exact affinity lies in [A - B, A + B], and 4 u covers the
+ *      library arccos, which is taken to be within one ulp of a value of at most pi / 2).
+ *      This is loose near A = 1, as any such distance is: about sqrt(2 B) at A = 1.
+ *   4. not promised bit for bit: independence of the order of a diagram's rows.  A term is a
+ *      function of its two points alone, so two row orders add the same terms, bit for bit, and
+ *      differ by the roundings of steps d, e, g and h only: at most 2 (2 M + 30) u, which is
+ *      below B as long as 2 M + 30 <= 2 T, that is for every M the entry accepts.  B is what
+ *      the tests hold two row orders to.
+ *
+ * Limits: at most TDA_PF_MAX_POINTS = 1024 finite points in a diagram that a pair names (no
+ * self is evaluated, so a larger diagram that no pair names is accepted), at most
+ * TDA_SW_MAX_WORK diagrams and pairs per call, and at most TDA_SW_MAX_WORK parts (above) over
+ * the call's pairs (the call's scratch, 24 bytes per part), else TDA_E_UNSUPPORTED.
+ * TDA_E_INVALID, in this order: args NULL, S < 0, offsets NULL, reserved != 0, sigma not
+ * finite, not > 0, or such that c2 is not a finite normal number, bad offsets, points NULL,
+ * P < 0; then TDA_E_UNSUPPORTED for too many diagrams or pairs, TDA_E_INVALID for a pair index
+ * outside [0, S), and TDA_E_UNSUPPORTED for a named diagram beyond the point limit and for too
+ * many parts.  All argument errors arrive before any device work.  Coordinates so large that
+ * b + d overflows are outside the definition (pi(p) is then infinite and a density may be NaN).
+ *
  * tda_persistence_curve: persistence curves (Chung and Lawson 2019) of S diagrams on a grid, in
  * one call: the Betti curve, the lifespan curve, the entropy summary function (Atienza,
  * Gonzalez-Diaz, Soriano-Trigueros 2020), the silhouette (Chazal et al. 2014) and any other sum of
@@ -467,6 +583,35 @@ typedef struct tda_hk_result {
 
 int tda_heat_kernel(const tda_hk_args *args, tda_hk_result **out);
 void tda_hk_free(tda_hk_result *r);
+
+#define TDA_PF_MAX_POINTS 1024 /* finite points of a diagram that a pair names          */
+#define TDA_PF_EXP_ULP 3       /* E of the accuracy bound B(n1, n2)                      */
+#define TDA_PF_CUT 708         /* a term whose argument is below -708 is +0.0            */
+#define TDA_PF_LANES 64        /* evaluation points of a part: enters the order of sums  */
+#define TDA_PF_CHUNK 128       /* sources staged at a time: does not enter the order     */
+
+typedef struct tda_pf_args {
+    const double *points;   /* host (total, 2) f64 (birth, death); non-finite rows are skipped */
+    const int64_t *offsets; /* host [S + 1] non-decreasing row boundaries, offsets[0] = 0      */
+    int64_t S;              /* diagrams                                                        */
+    const int32_t *pairs;   /* host (P, 2) diagram indices, or NULL: every i < j, row-major    */
+    int64_t P;              /* pairs in `pairs`; ignored when pairs is NULL                    */
+    double sigma;           /* finite, > 0, 1 / (2 sigma^2) a finite normal number             */
+    int32_t device;         /* HIP device ordinal                                              */
+    int32_t reserved;       /* must be 0                                                       */
+} tda_pf_args;
+
+typedef struct tda_pf_result {
+    int64_t P;          /* pairs computed (S (S - 1) / 2 when pairs was NULL)          */
+    const double *a;    /* host [P]: sum_z rhoU(z), U that of the pair's first diagram  */
+    const double *b;    /* host [P]: sum_z rhoV(z)                                      */
+    const double *h;    /* host [P]: sum_z sqrt(rhoU(z) rhoV(z))                        */
+    const double *dist; /* host [P]: fisher of each pair                                */
+    double device_ms;   /* device time of the call (HIP events, copies included)       */
+} tda_pf_result;
+
+int tda_persistence_fisher(const tda_pf_args *args, tda_pf_result **out);
+void tda_persistence_fisher_free(tda_pf_result *r);
 
 /* The Frechet mean (2-Wasserstein barycenter; Turner, Mileyko, Mukherjee, Harer 2014) of S diagrams:
  * the argument struct and the limits of an entry that is NOT in the library yet

@@ -441,6 +441,37 @@ TDA_HK_MAX_POINTS = 4096  # finite points of one diagram
 TDA_HK_EXP_ULP = 3  # E of the heat kernel's accuracy bound C(n1, n2)
 
 
+class PfArgs(ctypes.Structure):  # include/tda_dgm.h tda_pf_args
+    _fields_ = [
+        ("points", ctypes.c_void_p),
+        ("offsets", ctypes.c_void_p),
+        ("S", ctypes.c_int64),
+        ("pairs", ctypes.c_void_p),
+        ("P", ctypes.c_int64),
+        ("sigma", ctypes.c_double),
+        ("device", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class PfResult(ctypes.Structure):  # include/tda_dgm.h tda_pf_result
+    _fields_ = [
+        ("P", ctypes.c_int64),
+        ("a", ctypes.POINTER(ctypes.c_double)),
+        ("b", ctypes.POINTER(ctypes.c_double)),
+        ("h", ctypes.POINTER(ctypes.c_double)),
+        ("dist", ctypes.POINTER(ctypes.c_double)),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
+TDA_PF_MAX_POINTS = 1024  # finite points of a diagram that a pair names
+TDA_PF_EXP_ULP = 3  # E of the persistence Fisher accuracy bound B(n1, n2)
+TDA_PF_CUT = 708  # a term whose argument is below -708 is +0.0
+TDA_PF_LANES = 64  # evaluation points of a part
+TDA_PF_CHUNK = 128  # sources staged at a time
+
+
 class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
     _fields_ = [
         ("x_train", ctypes.c_void_p),
@@ -484,6 +515,7 @@ DGM_ENTRIES = {
     "pi": ("tda_persistence_image", "tda_pi_free", PiArgs, PiResult),
     "hk": ("tda_heat_kernel", "tda_hk_free", HkArgs, HkResult),
     "pc": ("tda_persistence_curve", "tda_pc_free", PcArgs, PcResult),
+    "pf": ("tda_persistence_fisher", "tda_persistence_fisher_free", PfArgs, PfResult),
 }
 # their symbols, one tuple per addition to the header
 DGM_EXPORTS = DGM_ENTRIES["sw"][:2]
@@ -492,6 +524,7 @@ WASSERSTEIN_EXPORTS = DGM_ENTRIES["ws"][:2]
 VECTOR_EXPORTS = DGM_ENTRIES["pl"][:2] + DGM_ENTRIES["pi"][:2]
 HEAT_EXPORTS = DGM_ENTRIES["hk"][:2]
 CURVE_EXPORTS = DGM_ENTRIES["pc"][:2]
+FISHER_EXPORTS = DGM_ENTRIES["pf"][:2]
 
 _lib = None
 

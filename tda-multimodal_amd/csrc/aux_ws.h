@@ -1,5 +1,5 @@
 // aux_ws.h -- the per-device workspace of the entries beside the persistence pipeline (UMAP, the
-// spectral metrics, greedy landmarks, resampling, the permutation test and the seven diagram entries, which use it through dgm_call.h),
+// spectral metrics, greedy landmarks, resampling, the permutation test and the eight diagram entries, which use it through dgm_call.h),
 // part of rips.hip's translation unit.  Each entry has a stream, buffers and a mutex of its own: no slot's stream is used and
 // nothing is captured into a graph.  The rules these entries share with the pipeline live in ws_life.h
 // and are kept by calling it: a buffer grows through ws::grow (a failed growth leaves it empty) under
@@ -10,7 +10,7 @@
 
 namespace {
 
-enum AuxEntry { kAuxUmap, kAuxSpectral, kAuxGreedy, kAuxResample, kAuxPerm, kAuxSw, kAuxBn, kAuxWs, kAuxPl, kAuxPi, kAuxHk, kAuxPc, kAuxEntries };
+enum AuxEntry { kAuxUmap, kAuxSpectral, kAuxGreedy, kAuxResample, kAuxPerm, kAuxSw, kAuxBn, kAuxWs, kAuxPl, kAuxPi, kAuxHk, kAuxPc, kAuxPf, kAuxEntries };
 
 struct AuxWs {
     int device = -1;

@@ -1,5 +1,5 @@
-// dgm_call.h -- the frame of a call of include/tda_dgm.h, shared by its seven entries (dgm_host.h,
-// bn_host.h, ws_host.h, vec_host.h, hk_host.h, pc_host.h), part of rips.hip's translation unit.
+// dgm_call.h -- the frame of a call of include/tda_dgm.h, shared by its eight entries (dgm_host.h,
+// bn_host.h, ws_host.h, vec_host.h, hk_host.h, pc_host.h, pf_host.h), part of rips.hip's translation unit.
 //
 // Every entry has one shape: plan on the host (dgm_plan.h), lay the call's buffer out -- the arrays
 // the device reads first, then the regions it only writes --, upload the first part in one copy,

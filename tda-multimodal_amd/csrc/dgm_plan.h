@@ -1,10 +1,11 @@
-// dgm_plan.h -- the host plans of the seven entries of include/tda_dgm.h, one per entry: sw_plan, bn_plan
+// dgm_plan.h -- the host plans of the eight entries of include/tda_dgm.h, one per entry: sw_plan, bn_plan
 // and ws_plan (PairPlan: the layout checks, the finite points and the pair list, the pairs sorted into size
 // classes and, for tda_wasserstein, oriented canonically), hk_plan (HkPlan: the work list of
-// tda_heat_kernel) and pl_plan / pi_plan / pc_plan (VecPlan: per diagram, at the end), each with the size classes
+// tda_heat_kernel), pf_plan (PfPlan: that of tda_persistence_fisher) and pl_plan / pi_plan / pc_plan (VecPlan: per
+// diagram, at the end), each with the size classes
 // of its launches.  Plain C++, no HIP: a plan returns an error code and leaves its message in `msg`
-// (tests/dgm_plan_main.cpp, ws_plan_main.cpp, hk_plan_main.cpp, vec_plan_main.cpp and pc_plan_main.cpp run them with a
-// host compiler alone).  The checks of a plan run in the order its entry has always made them.
+// (tests/dgm_plan_main.cpp, ws_plan_main.cpp, hk_plan_main.cpp, pf_plan_main.cpp, vec_plan_main.cpp and pc_plan_main.cpp run
+// them with a host compiler alone).  The checks of a plan run in the order its entry has always made them.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -279,6 +280,60 @@ inline int hk_plan(const tda_hk_args* a, HkPlan& hp, std::string& msg) {
     }
     if (hp.part_off[pl.P] > TDA_SW_MAX_WORK)
         return bad(TDA_E_UNSUPPORTED, "heat kernel: more than 2^27 parts of 64 x 256 terms in one call is not supported (split the pairs)");
+    return 0;
+}
+
+// ---------------------------------------------------------------- the persistence Fisher distance (tda_persistence_fisher)
+// The work list of a call: its P pairs and nothing else (no selfs), every one oriented canonically
+// (dgm_orient; swapped[p] tells which, so that a and b go back to the diagrams as the caller named
+// them) and cut into parts of kPfLanes evaluation points of Z = U then V (tda_dgm.h gives the order
+// of the sums that this constant fixes; kPfChunk only sizes the staging of the sources).
+
+constexpr int kPfLanes = TDA_PF_LANES;  // evaluation points of a part: one per lane of the part's wave
+constexpr int kPfChunk = TDA_PF_CHUNK;  // sources of U and of V staged in LDS at a time
+constexpr int kPfClassM[kPairClasses] = {64, 512, 2 * TDA_PF_MAX_POINTS};  // n1 + n2 at most: 2, 16 and 64 parts
+
+struct PfPlan {
+    PairPlan pl;                    // pl.pairs oriented
+    std::vector<uint8_t> swapped;   // [P]
+    std::vector<int64_t> part_off;  // [P + 1] into the parts, in the order of pl.pairs
+    int cls_parts[kPairClasses] = {};  // the largest number of parts of a pair of the class
+    double c2 = 0.0;
+};
+
+inline int64_t pf_parts(int64_t n1, int64_t n2) { return (2 * (n1 + n2) + kPfLanes - 1) / kPfLanes; }
+
+inline int pf_plan(const tda_pf_args* a, PfPlan& fp, std::string& msg) {
+    auto bad = [&](int code, const char* m) { return msg = m, code; };
+    if (int rc = dgm_check_head(a, msg)) return rc;
+    if (a->reserved != 0) return bad(TDA_E_INVALID, "reserved must be 0");
+    if (!std::isfinite(a->sigma) || !(a->sigma > 0.0)) return bad(TDA_E_INVALID, "sigma must be finite and > 0");
+    const double s2 = a->sigma * a->sigma;  // rounded; 2 s2 is exact (or overflows: c2 = 0, refused below)
+    fp.c2 = 1.0 / (2.0 * s2);
+    if (!std::isnormal(fp.c2)) return bad(TDA_E_INVALID, "sigma: 1 / (2 sigma^2) must be a finite normal number");
+    PairPlan& pl = fp.pl;
+    if (int rc = dgm_pairs(a, "persistence Fisher", 1, "persistence Fisher: more than 2^27 pairs in one call is not supported (split the pairs)", pl, msg))
+        return rc;
+    for (int64_t q = 0; q < 2 * pl.P; ++q) {  // only a diagram that a pair names is measured
+        const int32_t s = pl.pairs[q];
+        if (pl.off[s + 1] - pl.off[s] > TDA_PF_MAX_POINTS)
+            return bad(TDA_E_UNSUPPORTED, "persistence Fisher: a diagram with more than 1024 finite points is not supported");
+    }
+    if (int rc = dgm_classify(pl, PairSize::kSum, kPfClassM, "persistence Fisher: a diagram with more than 1024 finite points is not supported", msg))
+        return rc;
+    dgm_orient(pl, fp.swapped);
+    fp.part_off.assign((size_t)pl.P + 1, 0);
+    for (int64_t w = 0; w < pl.P; ++w) {
+        const int32_t i = pl.pairs[2 * w], j = pl.pairs[2 * w + 1];
+        const int64_t n1 = pl.off[i + 1] - pl.off[i], n2 = pl.off[j + 1] - pl.off[j];
+        const int64_t parts = pf_parts(n1, n2);
+        fp.part_off[w + 1] = fp.part_off[w] + parts;
+        int c = 0;
+        while (n1 + n2 > kPfClassM[c]) ++c;
+        fp.cls_parts[c] = std::max(fp.cls_parts[c], (int)parts);
+    }
+    if (fp.part_off[pl.P] > TDA_SW_MAX_WORK)
+        return bad(TDA_E_UNSUPPORTED, "persistence Fisher: more than 2^27 parts of 64 evaluation points in one call is not supported (split the pairs)");
     return 0;
 }
 

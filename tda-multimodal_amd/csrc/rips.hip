@@ -1201,3 +1201,5 @@ void tda_pipe_destroy(tda_pipe* pipe) { delete pipe; }
 #include "hk_host.h"
 // persistence curves: Betti, lifespan, entropy, silhouette (include/tda_dgm.h)
 #include "pc_host.h"
+// the persistence Fisher distance between persistence diagrams (include/tda_dgm.h)
+#include "pf_host.h"

@@ -25,7 +25,7 @@ import numpy as np
 from . import _lib, diagrams
 from .bootstrap import _check_count
 
-METRICS = ("sliced_wasserstein", "bottleneck", "wasserstein", "heat")
+METRICS = ("sliced_wasserstein", "bottleneck", "wasserstein", "heat", "fisher")
 
 
 def _codes(labels):
@@ -125,7 +125,7 @@ def diagram_permutation_test(dgms, labels, metric: str = "wasserstein", dim: int
                              **kw) -> PermutationTest:
     """The permutation test between groups of diagrams: one call to the ``metric``'s matrix entry
     (``wasserstein_matrix``, ``bottleneck_matrix``, ``sliced_wasserstein_matrix`` over ``M``
-    directions, or ``heat_matrix`` at scale ``sigma``), then :func:`permutation_test` on it with
+    directions, ``heat_matrix`` or ``fisher_matrix`` at scale ``sigma``), then :func:`permutation_test` on it with
     the remaining arguments (B, q, seed, permutations, return_null).  ``dgms`` is whatever those
     entries accept: a list of (n, 2) arrays, or of ``LayerResult`` (then diagram ``dim`` of each)."""
     if metric not in METRICS:
@@ -134,6 +134,8 @@ def diagram_permutation_test(dgms, labels, metric: str = "wasserstein", dim: int
         D = diagrams.sliced_wasserstein_matrix(dgms, M=M, device=device, dim=dim)
     elif metric == "heat":
         D = diagrams.heat_matrix(dgms, sigma=sigma, device=device, dim=dim)
+    elif metric == "fisher":
+        D = diagrams.fisher_matrix(dgms, sigma=sigma, device=device, dim=dim)
     elif metric == "bottleneck":
         D = diagrams.bottleneck_matrix(dgms, device=device, dim=dim)
     else:

@@ -28,7 +28,7 @@ import json
 
 import numpy as np
 
-from .diagrams import (betti_curves, bottleneck_matrix, entropy_curves, heat_matrix, lifespan_curves, persistence_images, persistence_landscapes,
+from .diagrams import (betti_curves, bottleneck_matrix, entropy_curves, fisher_matrix, heat_matrix, lifespan_curves, persistence_images, persistence_landscapes,
                        persistence_silhouettes, sliced_wasserstein_matrix, wasserstein_matrix)
 from .ripser import ripser_batch
 
@@ -110,9 +110,11 @@ def layer_distance_matrix(results, dim: int = 1, M: int = 50, device: int = 0, m
     ignored: diagrams.bottleneck_matrix; in the units of ``max_h1_persistence``, a
     layer's distance to an empty diagram being half of it), "wasserstein" (the
     optimal-transport distance in which every bar counts, M is ignored:
-    diagrams.wasserstein_matrix) or "heat" (the distance of the persistence
-    scale-space kernel at scale ``sigma``, which only this metric reads; M is
-    ignored: diagrams.heat_matrix).  Layers of equal
+    diagrams.wasserstein_matrix), "heat" (the distance of the persistence
+    scale-space kernel at scale ``sigma``; M is ignored: diagrams.heat_matrix)
+    or "fisher" (the persistence Fisher distance with a Gaussian of standard
+    deviation ``sigma``; M is ignored: diagrams.fisher_matrix).  Only these two
+    read ``sigma``, and one default serves both.  Layers of equal
     ``max_h1_persistence`` can hold quite different diagrams; this is the
     layer-against-layer view the per-layer records cannot give."""
     if metric == "bottleneck":
@@ -121,8 +123,10 @@ def layer_distance_matrix(results, dim: int = 1, M: int = 50, device: int = 0, m
         return wasserstein_matrix(results, device=device, dim=dim)
     if metric == "heat":
         return heat_matrix(results, sigma=sigma, device=device, dim=dim)
+    if metric == "fisher":
+        return fisher_matrix(results, sigma=sigma, device=device, dim=dim)
     if metric != "sliced_wasserstein":
-        raise ValueError(f"metric must be 'sliced_wasserstein', 'bottleneck', 'wasserstein' or 'heat', got {metric!r}")
+        raise ValueError(f"metric must be 'sliced_wasserstein', 'bottleneck', 'wasserstein' or 'heat', or 'fisher', got {metric!r}")
     return sliced_wasserstein_matrix(results, M=M, device=device, dim=dim)
 
 
