@@ -208,6 +208,17 @@ int tda_device_ok(int32_t device);
  * gram_layer: the whole-layer Gram kernel (f32, N <= 144) instead of 64x64
  * tiles.  Returns 0 or TDA_E_INVALID. */
 int tda_debug_dist_plan(int64_t N, int64_t D, int32_t dtype, int32_t *mfma, int32_t *dsplit, int32_t *gram_layer);
+/* Test hook: the attempts of the retry ladder that the last tda_rips_batch /
+ * tda_rips_dm entry on (device, slot) ran, in order, the one-layer sub-calls
+ * of a column-cap re-run appended.  TDA_ATTEMPT_FIELDS int64 per attempt:
+ * force_global, scale, force_big, no_par, no_cap, the error flags and the
+ * k_reduce_par code the ladder decided on, then the records, record keys,
+ * bucket keys and evictions the parallel reducer's last launch drew (read
+ * after an abort or under TDA_DEBUG; else -1).  At most cap / TDA_ATTEMPT_FIELDS
+ * records are written to out; returns the number of attempts, or
+ * TDA_E_INVALID. */
+#define TDA_ATTEMPT_FIELDS 11
+int tda_debug_attempts(int32_t device, int32_t slot, int64_t *out, int32_t cap);
 
 /*
  * Normalised effective dimensionality of B activation matrices (B, N, D):

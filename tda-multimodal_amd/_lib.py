@@ -503,7 +503,7 @@ class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
 # every symbol declared in include/tda_rips.h and include/tda_umap.h
 EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "tda_version", "tda_device_ok",
            "tda_effective_dim", "tda_effective_dim_windows", "tda_matrix_entropy", "tda_greedy_perm", "tda_greedy_free",
-           "tda_resample", "tda_resample_free", "tda_permutation_test", "tda_perm_free", "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan",
+           "tda_resample", "tda_resample_free", "tda_permutation_test", "tda_perm_free", "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan", "tda_debug_attempts",
            "tda_pipe_create", "tda_pipe_submit", "tda_pipe_flush", "tda_pipe_wait", "tda_pipe_release", "tda_pipe_destroy")
 # the entries of include/tda_dgm.h, all of one shape, int entry(const args*, result**) and void free(result*):
 # name -> (entry symbol, free symbol, args struct, result struct)
@@ -635,6 +635,8 @@ def lib():
     _i32p = ctypes.POINTER(ctypes.c_int32)
     L.tda_debug_dist_plan.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, _i32p, _i32p, _i32p]
     L.tda_debug_dist_plan.restype = ctypes.c_int
+    L.tda_debug_attempts.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32]
+    L.tda_debug_attempts.restype = ctypes.c_int
     L.tda_umap_batch.argtypes = [ctypes.POINTER(UmapArgs)]
     L.tda_umap_batch.restype = ctypes.c_int
     L.tda_effective_dim.argtypes = [ctypes.POINTER(EdArgs), _f32p]

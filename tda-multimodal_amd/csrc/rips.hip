@@ -133,6 +133,15 @@ struct Workspace {
         Attempt at;  // no_cap stays false: column caps are not remembered
     };
     std::vector<Retry> retry;
+    // test hook (tda_debug_attempts): one record per attempt of the last entry on this slot, in
+    // order, the sub-calls of a cap-miss re-run included; run_entry resets it
+    struct AttemptRec {
+        Attempt at;
+        int errs;            // what next_attempt was given
+        unsigned par_code;
+        int64_t rec_used, rpool_used, bpool_used, evictions;  // ParCtl at the attempt's end; -1: not read
+    };
+    std::vector<AttemptRec> attempts;
     std::mutex mu;
 };
 
@@ -702,6 +711,9 @@ void fill_graph_key(Call& c, ws::GraphKey& key) {
                      (p.wide ? 1 << 10 : 0) | (p.want64 ? 1 << 11 : 0) | (p.par2 ? 1 << 12 : 0) | (p.piv2_sparse ? 1 << 13 : 0) |
                      (p.dist.gram_layer ? 1 << 14 : 0);
         gk.dsplit = p.dist.dsplit;
+        gk.pool_shift = p.par ? par_pool_shift() : 0;
+        gk.par_steps[0] = p.par ? par_step_limit(1) : 0;
+        gk.par_steps[1] = p.par2 ? par_step_limit(2) : 0;
         gk.thresh = a.thresh;
         gk.n_label_sets = c.nls;
         gk.sil_K = c.sil_K;  // baked into the k_silhouette launch (argument K and its LDS size)
@@ -763,15 +775,22 @@ int collect_errors(Call& c, int& errs) {
 // what follows from the call's error flags (next_attempt, rips_retry.h); a failure sets the message
 int decide_retry(Call& c, int errs, RetryStep& step) {
     step = {RetryStep::kDone, c.at};
-    if (!errs) return 0;
     ParCtl ctl = {};
-    if (errs & (ERR_PAR | ERR_PAR2)) {
+    const bool par_err = (errs & (ERR_PAR | ERR_PAR2)) != 0;
+    // TDA_DEBUG: the pools a clean parallel reduction drew too (of its last launch: k_par_init zeroes them)
+    const bool read_ctl = par_err || (c.p.par && getenv("TDA_DEBUG"));
+    if (read_ctl) {
         HIPC(hipMemcpy(&ctl, c.B + c.p.o_pctl, sizeof(ctl), hipMemcpyDeviceToHost));
         if (getenv("TDA_DEBUG"))
-            fprintf(stderr, "[tda] k_reduce_par aborted: code %llu, evictions %llu, records %llu, pools %llu / %llu keys\n", ctl.err,
-                    ctl.evictions, ctl.rec_used, ctl.rpool_used, ctl.bpool_used);
+            fprintf(stderr, "[tda] k_reduce_par %s: code %llu, evictions %llu, records %llu, pools %llu / %llu keys\n",
+                    par_err ? "aborted" : "done", ctl.err, ctl.evictions, ctl.rec_used, ctl.rpool_used, ctl.bpool_used);
     }
-    const unsigned code = (unsigned)(ctl.err & 0xFFFF);
+    const unsigned code = par_err ? (unsigned)(ctl.err & 0xFFFF) : 0u;
+    if (read_ctl)
+        c.w.attempts.push_back({c.at, errs, code, (int64_t)ctl.rec_used, (int64_t)ctl.rpool_used, (int64_t)ctl.bpool_used, (int64_t)ctl.evictions});
+    else
+        c.w.attempts.push_back({c.at, errs, code, -1, -1, -1, -1});
+    if (!errs) return 0;
     step = next_attempt(errs, code, c.at, c.p.big, test_env_is("TDA_PAR_STRICT", "1"), test_env_is("TDA_REDUCE", "wave"));
     if (step.what != RetryStep::kFail) return 0;
     if (errs & (ERR_PAR | ERR_PAR2))
@@ -958,6 +977,11 @@ int run_pipeline(const tda_rips_args& a, int input_kind, const void* host_or_dev
             w.piv2_bytes = bytes;
         }
         w.piv2_dirty = true;  // until this call has cleared the words it set
+    } else {
+        // a plan without the sparse bitmap carves other buffers over the region a sparse plan left
+        // zero: the next sparse call on this slot starts from a full memset (the same address and
+        // size alone do not show it)
+        w.piv2_dirty = true;
     }
     if (int rc = launch_or_capture(c, gk)) return rc;
     if (a.want_dist) {
@@ -1010,6 +1034,11 @@ int run_attempts(const tda_rips_args& a, int input_kind, const void* src, tda_ri
 // entry: start from the configuration an earlier call of this shape ended on
 int run_entry(const tda_rips_args& a, int input_kind, const void* src, tda_rips_result** out) {
     Attempt at;
+    {
+        Workspace& w = *get_ws(a.device, a.slot);
+        std::lock_guard<std::mutex> g(w.mu);
+        w.attempts.clear();
+    }
     // not when a test forces a reducer (the memo would override what it asks for)
     if (!test_env_is("TDA_RETRY_MEMO", "0") && !test_env("TDA_REDUCE") && !test_env("TDA_PAR") && !test_env("TDA_PAR_STRICT") &&
         !test_env("TDA_CHAIN")) {
@@ -1108,6 +1137,25 @@ int tda_debug_dist_plan(int64_t N, int64_t D, int32_t dtype, int32_t* mfma, int3
     *dsplit = s.dsplit;
     *gram_layer = s.gram_layer ? 1 : 0;
     return 0;
+}
+
+// test hook: the attempts the last tda_rips_batch / tda_rips_dm entry on (device, slot) ran, in order
+// (cap-miss sub-calls appended): kAttemptFields int64 per attempt -- force_global, scale, force_big,
+// no_par, no_cap, errs, par_code (what next_attempt was given), then rec_used, rpool_used, bpool_used,
+// evictions of ParCtl where it was read (after an abort, or under TDA_DEBUG), else -1
+int tda_debug_attempts(int32_t device, int32_t slot, int64_t* out, int32_t cap) {
+    constexpr int kAttemptFields = TDA_ATTEMPT_FIELDS;
+    if (device < 0 || slot < 0 || slot >= TDA_MAX_SLOTS || cap < 0 || (cap > 0 && !out)) return fail(TDA_E_INVALID, "tda_debug_attempts: bad arguments");
+    Workspace& w = *get_ws(device, slot);
+    std::lock_guard<std::mutex> g(w.mu);
+    const int n = (int)w.attempts.size();
+    for (int i = 0; i < n && (i + 1) * kAttemptFields <= cap; ++i) {
+        const Workspace::AttemptRec& r = w.attempts[i];
+        const int64_t v[kAttemptFields] = {r.at.force_global, r.at.scale, r.at.force_big, r.at.no_par, r.at.no_cap, r.errs, (int64_t)r.par_code,
+                                           r.rec_used, r.rpool_used, r.bpool_used, r.evictions};
+        std::memcpy(out + (size_t)i * kAttemptFields, v, sizeof v);
+    }
+    return n;
 }
 
 int tda_device_ok(int32_t device) {

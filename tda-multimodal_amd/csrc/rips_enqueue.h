@@ -581,12 +581,15 @@ int enqueue_par(Call& c, int& start_dim) {
     // persistent workers (one 71-KB-LDS workgroup per CU by default); the surplus exits at once
     const unsigned par_grid = par_grid_size();
     const uint32_t* no_clr = nullptr;
+    ParBufs pb1 = pb, pb2 = pb;  // the reduction launches alone: each dimension's own step limit (tests)
+    pb1.step_limit = par_step_limit(1);
+    pb2.step_limit = par_step_limit(2);
     if (p.packed)
         hipLaunchKernelGGL((k_reduce_par<1, true>), dim3(par_grid), dim3(kParT), sizeof(ParLds), s, dist, n, L, stats, db[1], no_clr,
-                           (uint64_t)0, rb, pb, gb.dcode, gb.dsort, gb.ecap);
+                           (uint64_t)0, rb, pb1, gb.dcode, gb.dsort, gb.ecap);
     else
         hipLaunchKernelGGL((k_reduce_par<1, false>), dim3(par_grid), dim3(kParT), sizeof(ParLds), s, dist, n, L, stats, db[1], no_clr,
-                           (uint64_t)0, rb, pb, gb.dcode, gb.dsort, gb.ecap);
+                           (uint64_t)0, rb, pb1, gb.dcode, gb.dsort, gb.ecap);
     HIPC(hipGetLastError());
     MARK("k_reduce_par");
     // H2 next: residual H1 pivots into the dim-1 bitmap (k_reduce_par<2>) or map (k_reduce_big)
@@ -603,13 +606,13 @@ int enqueue_par(Call& c, int& start_dim) {
     HIPC(hipGetLastError());
     if (p.wide)  // N > 568: edge-code keys (k_edge_codes ran above)
         hipLaunchKernelGGL((k_reduce_par<2, false, true>), dim3(par_grid), dim3(kParT), sizeof(ParLds), s, dist, n, L, stats,
-                           db[2], (const uint32_t*)db[1].pivbits, db[1].piv_words, rb, pb, gb.dcode, gb.dsort, gb.ecap);
+                           db[2], (const uint32_t*)db[1].pivbits, db[1].piv_words, rb, pb2, gb.dcode, gb.dsort, gb.ecap);
     else if (n <= kPar2PackedMaxN)
         hipLaunchKernelGGL((k_reduce_par<2, true>), dim3(par_grid), dim3(kParT), sizeof(ParLds), s, dist, n, L, stats, db[2],
-                           (const uint32_t*)db[1].pivbits, db[1].piv_words, rb, pb, gb.dcode, gb.dsort, gb.ecap);
+                           (const uint32_t*)db[1].pivbits, db[1].piv_words, rb, pb2, gb.dcode, gb.dsort, gb.ecap);
     else
         hipLaunchKernelGGL((k_reduce_par<2, false>), dim3(par_grid), dim3(kParT), sizeof(ParLds), s, dist, n, L, stats, db[2],
-                           (const uint32_t*)db[1].pivbits, db[1].piv_words, rb, pb, gb.dcode, gb.dsort, gb.ecap);
+                           (const uint32_t*)db[1].pivbits, db[1].piv_words, rb, pb2, gb.dcode, gb.dsort, gb.ecap);
     HIPC(hipGetLastError());
     MARK("k_reduce_par<2>");
     hipLaunchKernelGGL(k_par_emit<2>, dim3(L), dim3(1024), 0, s, stats, db[2], rb, pb, c.pairs2, p.pcap[2], 0,

@@ -62,10 +62,12 @@ struct GraphKey {
     int64_t L, N, D;
     int maxdim, dtype, input_kind, x_on_device, flags, force_global, scale, force_big, variant, n_label_sets, sil_K, no_par, twonn, no_cap;
     int dsplit;  // K slices of the distance kernels (TDA_DIST_SPLIT can change them at the same (N, D): other launches, other offsets)
+    int pool_shift;  // TDA_PAR_POOL_SHIFT (tests): other pool capacities, other offsets behind them
     float thresh, tn_eps, capf;
     double tn_discard;
     const void* x;
     uint64_t gen;
+    uint64_t par_steps[2];  // the step limits baked into the k_reduce_par launches of H1 and H2 (TDA_PAR_STEPS_H1 / _H2, TDA_STEP_LIMIT)
 };
 // The one way to build a key: every byte zeroed (the padding too), then fill(k) sets the fields,
 // so keys of equal fields are equal bytes.  (-0.0f and 0.0f differ, as they always have.)

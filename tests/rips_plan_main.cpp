@@ -5,7 +5,8 @@
 // it prints the line back after "case" and then every field of the Plan that make_plan builds for
 // it as name=value (arrays as a,b,c,d; rcfg and the DistSel included), grouped by consumer.  The
 // test knobs are read from the environment, as in the library.  make_plan runs twice per case and
-// the program fails (exit 3) if the two plans differ in any printed field.
+// the program fails (exit 3) if the two plans differ in any printed field.  The knobs that are no
+// field of a Plan go to stderr, one line: step_limit, par_step_limit(1), par_step_limit(2), par_pool_shift.
 #include <cstdio>
 #include <string>
 
@@ -55,6 +56,8 @@ static std::string print(const Plan& p) {
 int main() {
     printf("sizeof Pair=%zu LayerStats=%zu BorCtl=%zu ParCtl=%zu kLdsMax=%d kDenseMaxN=%d\n", sizeof(Pair), sizeof(LayerStats), sizeof(BorCtl),
            sizeof(ParCtl), kLdsMax, kDenseMaxN);
+    fprintf(stderr, "knobs step_limit=%llu par_steps_h1=%llu par_steps_h2=%llu par_pool_shift=%d\n", (unsigned long long)step_limit(),
+            (unsigned long long)par_step_limit(1), (unsigned long long)par_step_limit(2), par_pool_shift());
     long long L, N, D;
     int maxdim, dtype, is_dist, want64, fg, scale, fb, no_par;
     while (scanf("%lld %lld %lld %d %d %d %d %d %d %d %d", &L, &N, &D, &maxdim, &dtype, &is_dist, &want64, &fg, &scale, &fb, &no_par) == 11) {

@@ -128,8 +128,13 @@ def test_grid144_maxdim2_vs_oracle(gpu, oracle, monkeypatch, reduce_kernel):
 
 @pytest.mark.parametrize("reduce_kernel,seed", [("auto", 1), ("big", 1), ("wave", 0)])
 def test_torus256_maxdim2_vs_oracle(gpu, oracle, monkeypatch, reduce_kernel, seed):
-    """seed 1 overflows the one-wave kernel's working column at scale 0; the
-    auto policy must then finish on the radix-heap kernel."""
+    """torus256 at maxdim 2 under each reducer policy.  `auto` and `big` both run
+    H1 and H2 on the parallel reducer k_reduce_par (the default for every
+    N > 64; TDA_REDUCE=big only forces the big path, tests/test_rips_plan_cpu.py),
+    `wave` one wave per layer on a seed whose working column fits.  The rung
+    this test was first written for -- seed 1 overflows the one-wave kernel and
+    the call finishes on the radix-heap kernel -- is walked, with its attempt
+    list asserted, by tests/test_retry_paths.py (TDA_PAR=0)."""
     monkeypatch.setenv("TDA_REDUCE", reduce_kernel)
     X = gpu.synthetic.torus(256, seed=seed)
     res = gpu.ripser_batch(X[None], maxdim=2)[0]

@@ -9,7 +9,10 @@ undefined-behaviour sanitizers and run as a program of its own, once per environ
 * invariants of every plan (alignment, regions that do not overlap, LDS sizes, reducer selection),
   from sizes restated here, for the pin's cases and for random shapes;
 * a test knob forces the field it is named for at the shapes where the GPU tests set it, and
-  changes nothing without TDA_TEST_OVERRIDES=1.
+  changes nothing without TDA_TEST_OVERRIDES=1;
+* the knobs of tests/test_retry_paths.py: TDA_PAR_POOL_SHIFT changes the four pool capacities of
+  k_reduce_par (their growing parts only) and the offsets behind them, nothing else;
+  TDA_PAR_STEPS_H1 / _H2 set the step limit of one k_reduce_par launch and leave step_limit() alone.
 """
 import math
 import os
@@ -249,6 +252,68 @@ def test_forced_variant_names_what_it_runs(exe, knobs, shapes, want):
             if k in want and q["dense"]:
                 assert q[k] == v, (c, k)
     assert plans_of(exe, cs, knobs, gate=False) == plain  # no gate: the knobs change nothing
+
+
+# ---- the knobs of tests/test_retry_paths.py
+PAR_RESERVE = 512 * 65 * 3840  # kParGrid * kParLv * chunk_start(4): every workgroup's first bucket chunks
+POOL_CAPS = ("rec_cap", "rpool_cap", "bpool_cap", "rq_cap")
+POOL_SHAPES = [case(2, 256, maxdim=2, scale=s) for s in range(5)] + [case(1, 300, maxdim=2, scale=s) for s in (0, 2)] + \
+    [case(1, 256, maxdim=1), case(4, 256, maxdim=2, no_par=1), case(1, 1025, maxdim=2, scale=1), case(1, 256, 256, 2, F64, is_dist=1)]
+
+
+@pytest.mark.parametrize("k", [1, 3, 9, 17, 30])
+def test_pool_shift_changes_the_four_capacities_and_what_lies_behind(exe, k):
+    knobs = {"TDA_PAR_POOL_SHIFT": str(k)}
+    plain = plans_of(exe, POOL_SHAPES)
+    for c, p, q in zip(POOL_SHAPES, plans_of(exe, POOL_SHAPES, knobs), plain):
+        scale = c[8]
+        assert q["par"] == 1
+        # the growing part shifted, after the << scale; the fixed parts as they were
+        assert p["rec_cap"] == ((q["rec_cap"] - (4096 << scale)) >> k) + (4096 << scale), c
+        assert p["rpool_cap"] == q["rpool_cap"] >> k, c
+        assert p["bpool_cap"] == ((q["bpool_cap"] - PAR_RESERVE) >> k) // 256 * 256 + PAR_RESERVE, c
+        assert p["rq_cap"] == max(1, q["rq_cap"] >> k), c
+        assert all(p[f] < q[f] for f in POOL_CAPS), c
+        # nothing else but the offsets carved behind the first pool that shrank, and the total
+        behind = {f for f, v in q.items() if f.startswith("o_") and (max(v) if isinstance(v, list) else v) > q["o_prec"]} | {"total"}
+        changed = {f for f in q if p[f] != q[f]}
+        assert set(POOL_CAPS) <= changed <= set(POOL_CAPS) | behind, (c, sorted(changed - behind))
+        assert {"o_prpool", "o_pbpool", "o_prq", "total"} <= changed, c
+        check_invariants(c, p, knobs_set=True)
+    assert plans_of(exe, POOL_SHAPES, knobs, gate=False) == plain  # no gate: the knob changes nothing
+    # no parallel reducer in the plan: nothing to change
+    serial = [case(32, 48, maxdim=2), case(1, 256, maxdim=2, no_par=2), case(1, 300, maxdim=0)]
+    assert plans_of(exe, serial, knobs) == plans_of(exe, serial)
+
+
+@pytest.mark.parametrize("k", [1, 6, 13, 30])
+def test_invariants_of_random_shapes_with_the_pool_shift(exe, k):
+    cs = random_cases(200, 11 + k)
+    assert any(p["par"] for p in plans_of(exe, cs))
+    for c, p in zip(cs, plans_of(exe, cs, {"TDA_PAR_POOL_SHIFT": str(k)})):
+        check_invariants(c, p)
+
+
+def knob_line(exe, knobs=None, gate=True):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("TDA_")}
+    env.update(knobs or {})
+    if gate:
+        env["TDA_TEST_OVERRIDES"] = "1"
+    err = subprocess.run([exe], input="", capture_output=True, text=True, check=True, env=env).stderr
+    return dict((k, int(v)) for k, v in (t.split("=") for t in err.split()[1:]))
+
+
+def test_par_step_knobs_set_one_launch_each(exe):
+    plain = dict(step_limit=1 << 26, par_steps_h1=1 << 26, par_steps_h2=1 << 26, par_pool_shift=0)
+    assert knob_line(exe) == plain
+    assert knob_line(exe, {"TDA_PAR_STEPS_H1": "4"}) == dict(plain, par_steps_h1=4)
+    assert knob_line(exe, {"TDA_PAR_STEPS_H2": "4"}) == dict(plain, par_steps_h2=4)
+    assert knob_line(exe, {"TDA_STEP_LIMIT": "99", "TDA_PAR_STEPS_H2": "7"}) == dict(plain, step_limit=99, par_steps_h1=99, par_steps_h2=7)
+    assert knob_line(exe, {"TDA_PAR_POOL_SHIFT": "5"}) == dict(plain, par_pool_shift=5)
+    assert knob_line(exe, {"TDA_PAR_STEPS_H1": "4", "TDA_PAR_STEPS_H2": "4", "TDA_PAR_POOL_SHIFT": "5", "TDA_STEP_LIMIT": "9"}, gate=False) == plain
+    # the serial kernels' step limit (rcfg) does not follow the parallel knobs
+    cs = [case(1, 256, maxdim=2)]
+    assert plans_of(exe, cs, {"TDA_PAR_STEPS_H1": "4", "TDA_PAR_STEPS_H2": "4"}) == plans_of(exe, cs)
 
 
 if __name__ == "__main__":

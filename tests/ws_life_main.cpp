@@ -174,8 +174,8 @@ GraphKey key_of(const GraphCache& gc, const std::function<void(GraphKey&)>& twea
     make_key(k, [&](GraphKey& g) {
         g.L = 32, g.N = 48, g.D = 3;
         g.maxdim = 2, g.dtype = 1, g.input_kind = 0, g.x_on_device = 1, g.flags = 4, g.force_global = 0, g.scale = 1, g.force_big = 0;
-        g.variant = 0x1234, g.n_label_sets = 2, g.sil_K = 5, g.no_par = 0, g.twonn = 1, g.no_cap = 0, g.dsplit = 2;
-        g.thresh = 0.0f, g.tn_eps = 1e-6f, g.capf = 0.5f, g.tn_discard = 0.1, g.x = &g_stream, g.gen = gc.gen();
+        g.variant = 0x1234, g.n_label_sets = 2, g.sil_K = 5, g.no_par = 0, g.twonn = 1, g.no_cap = 0, g.dsplit = 2, g.pool_shift = 0;
+        g.thresh = 0.0f, g.tn_eps = 1e-6f, g.capf = 0.5f, g.tn_discard = 0.1, g.x = &g_stream, g.gen = gc.gen(), g.par_steps[0] = g.par_steps[1] = 1ull << 26;
         if (tweak) tweak(g);
     });
     return k;
@@ -347,10 +347,11 @@ void cache_hit_miss_evict() {
         [](GraphKey& g) { ++g.sil_K; }, [](GraphKey& g) { ++g.no_par; }, [](GraphKey& g) { ++g.twonn; }, [](GraphKey& g) { ++g.no_cap; },
         [](GraphKey& g) { ++g.dsplit; }, [](GraphKey& g) { g.thresh = -0.0f; }, [](GraphKey& g) { g.thresh = 1.0f; },
         [](GraphKey& g) { g.tn_eps *= 2; }, [](GraphKey& g) { g.capf *= 2; }, [](GraphKey& g) { g.tn_discard *= 2; },
-        [](GraphKey& g) { g.x = &g_ev0; }, [](GraphKey& g) { ++g.gen; }};
-    // every member is in the list (thresh twice): 3 of 8 bytes, 15 ints, 3 floats, then 3 of 8 bytes
-    static_assert(sizeof(GraphKey) == 3 * 8 + 15 * 4 + 3 * 4 + 3 * 8, "GraphKey changed: bring `fields` up to date");
-    CHECK(fields.size() == 3 + 15 + 3 + 3 + 1);
+        [](GraphKey& g) { g.x = &g_ev0; }, [](GraphKey& g) { ++g.gen; }, [](GraphKey& g) { ++g.pool_shift; },
+        [](GraphKey& g) { g.par_steps[0] = 4; }, [](GraphKey& g) { g.par_steps[1] = 4; }};
+    // every member is in the list (thresh twice): 3 of 8 bytes, 16 ints, 3 floats (and 4 bytes of padding), then 5 of 8 bytes
+    static_assert(sizeof(GraphKey) == 3 * 8 + 16 * 4 + 3 * 4 + 4 + 5 * 8, "GraphKey changed: bring `fields` up to date");
+    CHECK(fields.size() == 3 + 16 + 3 + 5 + 1);
     for (const auto& f : fields) CHECK(gc.find(key_of(gc, f)) == nullptr);
 
     // equal fields over differently filled memory: equal bytes
