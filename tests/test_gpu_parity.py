@@ -230,7 +230,13 @@ def test_torch_device_input(gpu, oracle):
 @pytest.mark.parametrize("chain", ["auto", "fast", "general"])
 def test_dense_chain_ties_vs_oracle(gpu, oracle, monkeypatch, chain):
     """N <= 64 clouds with many equal edge lengths (integer grids, small
-    integer coordinates): the tie-class pivot path of every H1-chain variant."""
+    integer coordinates): the tie-class pivot path of the H1-chain variants.
+    Which variant runs: at N = 48 and 40 `auto` is TABLE, `fast` FAST and
+    `general` GENERAL.  At N = 64 all three run GENERAL: K = 21 is above
+    kChainFastMaxK, so the plan honours neither `fast` nor `auto`'s TABLE
+    (tests/test_rips_plan_cpu.py, test_size_borders_forced_variants).  The
+    forced variants at the sizes where they do differ from the default, ties
+    included, are run by tests/test_size_borders.py."""
     monkeypatch.setenv("TDA_CHAIN", chain)
     rng = np.random.default_rng(5)
     g2 = np.array([(i, j) for i in range(6) for j in range(8)], np.float32)

@@ -12,7 +12,10 @@ undefined-behaviour sanitizers and run as a program of its own, once per environ
   changes nothing without TDA_TEST_OVERRIDES=1;
 * the knobs of tests/test_retry_paths.py: TDA_PAR_POOL_SHIFT changes the four pool capacities of
   k_reduce_par (their growing parts only) and the offsets behind them, nothing else;
-  TDA_PAR_STEPS_H1 / _H2 set the step limit of one k_reduce_par launch and leave step_limit() alone.
+  TDA_PAR_STEPS_H1 / _H2 set the step limit of one k_reduce_par launch and leave step_limit() alone;
+* the size borders of tests/size_borders.py, which tests/test_size_borders.py runs on a device: the
+  plan changes kernel, instantiation, LDS layout or key format at exactly the N listed there (the
+  dense borders are in this test and not in the pin's NS: the pin would outgrow its size rule).
 """
 import math
 import os
@@ -21,6 +24,8 @@ import subprocess
 import sys
 
 import pytest
+
+import size_borders as sb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "tda-multimodal_amd", "csrc")
@@ -314,6 +319,91 @@ def test_par_step_knobs_set_one_launch_each(exe):
     # the serial kernels' step limit (rcfg) does not follow the parallel knobs
     cs = [case(1, 256, maxdim=2)]
     assert plans_of(exe, cs, {"TDA_PAR_STEPS_H1": "4", "TDA_PAR_STEPS_H2": "4"}) == plans_of(exe, cs)
+
+
+# ---- the size borders that tests/test_size_borders.py runs on a device (tests/size_borders.py)
+def border_case(n, L=1):
+    return case(L, n, maxdim=2)
+
+
+def test_size_borders_are_where_the_plan_changes(exe):
+    """Every N in 3 .. PLAN_SCAN_MAX at which the plan of (L = 1, N, D = 3, maxdim = 2) changes a field of
+    PLAN_FIELDS is a border of PLAN_BORDERS, with the fields and the values on both sides named there,
+    and the other way round.  A moved constant fails here, and the message says where the plan
+    changes now: the sizes tests/size_borders.py, and through it the GPU file, must move to."""
+    ns = list(range(2, sb.PLAN_SCAN_MAX + 1))
+    plans = dict(zip(ns, plans_of(exe, [border_case(n) for n in ns])))
+    found = []
+    for n in ns[1:]:
+        diff = {k: (plans[n - 1][k], plans[n][k]) for k in sb.PLAN_FIELDS if plans[n - 1][k] != plans[n][k]}
+        if diff:
+            found.append((n, diff))
+    want = [(n, {k: v for k, v in f.items() if k in sb.PLAN_FIELDS}) for n, f in sb.PLAN_BORDERS]
+    fd, wd = dict(found), dict(want)
+    assert found == want, "the plan changes at N = %s, tests/size_borders.py says %s; move these:\n%s" % (
+        [n for n, _ in found], [n for n, _ in want],
+        "\n".join("  N = %d: the plan changes %r, the file says %r" % (n, fd.get(n), wd.get(n)) for n in sorted(set(fd) | set(wd)) if fd.get(n) != wd.get(n)))
+    # the LDS sizes that decide a border, as literals
+    for n, f in sb.PLAN_BORDERS:
+        for k in ("chain_lds", "p1_lds"):
+            if k in f:
+                assert (plans[n - 1][k], plans[n][k]) == f[k], (n, k)
+    # what the list is read for: the state on the lower side, and the sizes the GPU file runs
+    for n, _ in sb.PLAN_BORDERS:
+        assert sb.plan_below(n) == {k: plans[n - 1][k] for k in sb.PLAN_FIELDS}, n
+    # the sizes that follow from PLAN_BORDERS, restated: after PLAN_BORDERS has moved these literals move too
+    moved = "derived from PLAN_BORDERS; if PLAN_BORDERS was moved on purpose, restate this literal here"
+    assert sb.DENSE_NS == (24, 25, 30, 31, 34, 35, 37, 38, 42, 43, 49, 50, 52, 53, 54, 59, 60, 61, 64, 65), moved
+    assert sb.FORCED_CHAIN_NS == (24, 30, 34, 37, 42, 49, 52) and sb.P1_NS == (60,), moved
+    assert [n for n, _ in sb.BIG_CASES] == [568, 569, 1024, 1025]
+
+
+def test_size_borders_lds_margins(exe):
+    """N = 60 is the last size whose two k_h2_phase1 waves fit: 159,920 of 163,840 bytes.  At 61 two
+    waves would need 169,248, so the plan has one; TABLE stops fitting at K = 12 and FAST at N = 53."""
+    p49, p50, p52, p53, p60, p61 = plans_of(exe, [border_case(n) for n in (49, 50, 52, 53, 60, 61)])
+    assert sb.K_LDS_MAX == K_LDS_MAX == 163840
+    assert p60["p1_waves"] == 2 and p60["p1_lds"] == 159920 <= K_LDS_MAX
+    shared = 16 + (4 * 61 * 61 + 15) // 16 * 16 + 2 * p61["n2p"]  # the matrix and the class table; n2p is a multiple of 8
+    two = shared + 2 * (p61["p1_lds"] - shared)
+    assert p61["p1_waves"] == 1 and two == sb.P1_TWO_WAVES_AT_61 > K_LDS_MAX
+    assert (p49["cmode"], p49["chain_lds"]) == (sb.CHAIN_TABLE, 161856) and p49["chain_lds"] <= K_LDS_MAX
+    assert (p50["cmode"], p50["chain_lds"]) == (sb.CHAIN_FAST, 141344)
+    assert (p52["cmode"], p52["chain_lds"]) == (sb.CHAIN_FAST, 157488) and (p53["cmode"], p53["chain_lds"]) == (sb.CHAIN_GENERAL, 94384)
+    # the L of the GPU cases changes no field of the borders
+    keys = sb.PLAN_FIELDS + ("chain_lds", "p1_lds")
+    ns = sb.DENSE_NS + sb.MID_NS
+    one = plans_of(exe, [border_case(n) for n in ns])
+    for L in (sb.DENSE_L, sb.MID_L) + sb.L_BORDERS:
+        for n, p, q in zip(ns, one, plans_of(exe, [border_case(n, L) for n in ns])):
+            assert [q[k] for k in keys] == [p[k] for k in keys], (L, n)
+
+
+def test_size_borders_forced_variants(exe):
+    """What the knobs of tests/test_size_borders.py force at its sizes.  TDA_CHAIN=fast is honoured
+    while FAST fits (cmode 1 up to N = 52) and silently gives GENERAL from 53 on: the forced `fast`
+    tie case of tests/test_gpu_parity.py at N = 64 (D = 4) runs GENERAL."""
+    cs = [border_case(n, sb.DENSE_L) for n in sb.FORCED_CHAIN_NS]
+    plain = plans_of(exe, cs)
+    fast, general = plans_of(exe, cs, {"TDA_CHAIN": "fast"}), plans_of(exe, cs, {"TDA_CHAIN": "general"})
+    for c, q, f, g in zip(cs, plain, fast, general):
+        assert q["cmode"] == sb.plan_below(c[1] + 1)["cmode"] != sb.CHAIN_GENERAL, c
+        assert f["cmode"] == sb.CHAIN_FAST and f["fast"] == 1 and g["cmode"] == sb.CHAIN_GENERAL and g["fast"] == 0, c
+        assert f["dK"] == g["dK"] == q["dK"] and f["dense"] == g["dense"] == 1, c
+        check_invariants(c, f, knobs_set=True)
+        check_invariants(c, g, knobs_set=True)
+    # forced fast is another variant than the default's everywhere but at 52, where FAST is the default
+    assert [c[1] for c, q, f in zip(cs, plain, fast) if f["cmode"] == q["cmode"]] == [52]
+    at52, at53, tie64 = plans_of(exe, [border_case(52), border_case(53), case(2, 64, 4, 2)], {"TDA_CHAIN": "fast"})
+    assert at52["cmode"] == sb.CHAIN_FAST and at53["cmode"] == sb.CHAIN_GENERAL and tie64["cmode"] == sb.CHAIN_GENERAL and tie64["dense"] == 1
+    cs = [border_case(n, sb.DENSE_L) for n in sb.P1_NS]
+    for c, q, p in zip(cs, plans_of(exe, cs), plans_of(exe, cs, {"TDA_P1_WAVES": "1"})):
+        assert q["p1_waves"] == 2 and p["p1_waves"] == 1 and p["p1_lds"] < q["p1_lds"], c
+        check_invariants(c, p, knobs_set=True)
+        # the knob moves these two fields only.  Neither is part of a captured graph's key (fill_graph_key
+        # in csrc/rips.hip), so on a device such a call can replay the two-wave graph of the default
+        # call of its shape: the GPU file has no TDA_P1_WAVES case (DESIGN.md 6.32, left out)
+        assert {k for k in q if q[k] != p[k]} == {"p1_waves", "p1_lds"}, c
 
 
 if __name__ == "__main__":
