@@ -4,7 +4,8 @@
 // Every entry has one shape: plan on the host (dgm_plan.h), lay the call's buffer out -- the arrays
 // the device reads first, then the regions it only writes --, upload the first part in one copy,
 // launch, download one region, and time the whole between two events of the entry's workspace
-// (aux_ws.h).  An entry says what it uploads and what it needs (upload, device), then
+// (aux_ws.h, through the steps of side_call.h's frame, on which this one sits).  An entry says what
+// it uploads and what it needs (upload, device), then
 //     begin   the workspace of (entry, device), its lock for the rest of the call, the stream and
 //             the two events, the kernel's dynamic-LDS limit if it needs one, the buffer,
 //             ev[0], the upload;
@@ -13,10 +14,11 @@
 // begin and end return an error code (HIPC returns from the function it stands in).
 #pragma once
 #include "dgm_plan.h"
+#include "side_call.h"
 
 namespace {
 
-struct DgmCall {
+struct DgmCall : SideCall {
     // `bytes` at p, uploaded by begin: its 256-byte-aligned offset in the call's buffer
     size_t upload(const void* p, size_t bytes) {
         const size_t o = cv.take(bytes);
@@ -35,28 +37,17 @@ struct DgmCall {
         host.resize(up_bytes);
         for (const Item& i : items)
             if (i.bytes) std::memcpy(host.data() + i.at, i.p, i.bytes);
-        w = &aux_ws(entry, dev);
-        guard = std::unique_lock<std::mutex>(w->mu);
-        if (int rc = aux_open(*w, 2)) return rc;
+        if (int rc = open(entry, dev, 2)) return rc;
         if (lds_fn)
-            if (int rc = aux_lds_attr(*w, lds_fn, lds_bytes)) return rc;
-        if (int rc = aux_reserve(*w, cv.o)) return rc;
-        HIPC(hipEventRecord(w->ev[0], w->stream));
-        HIPC(hipMemcpyAsync(w->buf.p, host.data(), up_bytes, hipMemcpyHostToDevice, w->stream));
+            if (int rc = lds_attr(lds_fn, lds_bytes)) return rc;
+        if (int rc = reserve(cv.o)) return rc;
+        if (int rc = start()) return rc;
+        HIPC(hipMemcpyAsync(buf(), host.data(), up_bytes, hipMemcpyHostToDevice, stream()));
         return 0;
-    }
-    float ms = 0.0f;  // end: the device time between the two events
-    hipStream_t stream() const { return w->stream; }
-    template <typename T>
-    T* at(size_t offset) const {
-        return (T*)(w->buf.p + offset);
     }
     int end(void* dst, size_t offset, size_t bytes) {
-        HIPC(hipMemcpyAsync(dst, w->buf.p + offset, bytes, hipMemcpyDeviceToHost, w->stream));
-        HIPC(hipEventRecord(w->ev[1], w->stream));
-        HIPC(hipStreamSynchronize(w->stream));
-        HIPC(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        return 0;
+        HIPC(hipMemcpyAsync(dst, buf() + offset, bytes, hipMemcpyDeviceToHost, stream()));
+        return finish();  // ms: the device time between the two events
     }
 
 private:
@@ -69,8 +60,6 @@ private:
     std::vector<Item> items;
     size_t up_bytes = 0;
     std::vector<char> host;  // the upload, packed
-    AuxWs* w = nullptr;
-    std::unique_lock<std::mutex> guard;  // w->mu, until the frame goes
 };
 
 // the four arrays of a PairPlan, uploaded first and in this order
@@ -79,12 +68,10 @@ struct PairAt {
     PairAt(DgmCall& call, const PairPlan& pl) : pts(call.upload(pl.pts)), off(call.upload(pl.off)), pairs(call.upload(pl.pairs)), order(call.upload(pl.order)) {}
 };
 
-// an entry's return, with or without a launch: the result handed to the caller
+// an entry's return, with or without a launch: side_return
 template <typename Impl, typename Pub>
 int dgm_return(std::unique_ptr<Impl>& R, Pub** out, float ms = 0.0f) {
-    R->pub.device_ms = ms;
-    *out = &R.release()->pub;
-    return 0;
+    return side_return(R, out, ms);
 }
 
 }  // namespace

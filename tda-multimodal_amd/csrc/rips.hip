@@ -36,6 +36,7 @@
 #include "rips_reduce_small.h"
 #include "rips_retry.h"
 #include "rips_plan.h"
+#include "side_plan.h"
 #include "ws_life.h"
 
 using namespace tda;
@@ -1227,6 +1228,7 @@ void tda_pipe_destroy(tda_pipe* pipe) { delete pipe; }
 }  // extern "C"
 
 #include "aux_ws.h"  // the per-device workspace of the entries below, and its locking
+#include "side_call.h"  // the frame of a call of theirs (their host plans: side_plan.h, dgm_plan.h)
 // UMAP embedding (include/tda_umap.h): same library, same error state
 #include "umap_host.h"
 // effective dimensionality (include/tda_rips.h tda_effective_dim)

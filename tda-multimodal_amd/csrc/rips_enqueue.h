@@ -220,6 +220,37 @@ int launch_point_distances(hipStream_t s, const DistLaunch& d, Mark&& mark) {
     return 0;
 }
 
+// (L, n, n) distance matrices of either dtype -> the f32 matrices every entry works on (upper triangle, diagonal 0)
+void launch_square_dist(hipStream_t s, const void* x, int dtype, int n, int L, float* dist) {
+    const unsigned gx = (unsigned)std::min<uint64_t>(1024, ((uint64_t)n * n + 255) / 256);
+    if (dtype == TDA_F64)
+        hipLaunchKernelGGL(k_square_dist<double>, dim3(gx, L), dim3(256), 0, s, (const double*)x, n, dist);
+    else
+        hipLaunchKernelGGL(k_square_dist<float>, dim3(gx, L), dim3(256), 0, s, (const float*)x, n, dist);
+}
+
+// The f32 matrices of a chunk of lc layers at x (points, or distance matrices: is_dist), into sq.o_dm of the
+// workspace at B (SqDistPlan, side_plan.h): host input goes through sq.o_x first; staged() queues what else the
+// entry uploads per chunk, where it always has (after the input).
+template <class Staged>
+int enqueue_chunk_distances(hipStream_t s, char* B, const SqDistPlan& sq, const void* x, int dtype, int64_t D, bool is_dist, size_t lc, Staged&& staged) {
+    if (sq.host_in) {
+        HIPC(hipMemcpyAsync(B + sq.o_x, x, lc * sq.x_layer, hipMemcpyHostToDevice, s));
+        x = B + sq.o_x;
+    }
+    if (int rc = staged()) return rc;
+    float* dm = (float*)(B + sq.o_dm);
+    if (!is_dist) {
+        HIPC(hipMemsetAsync(B + sq.o_rm, 0, lc * sq.N * 4, s));  // the distance kernels fold row maxima in (unused by these entries)
+        const DistLaunch dl = {x, dtype, (int)sq.N, D, (int)lc, sq.sel, dm, (uint32_t*)(B + sq.o_rm), (double*)(B + sq.o_gp), (double*)(B + sq.o_np), nullptr};
+        if (int rc = launch_point_distances(s, dl, [](const char*) { return 0; })) return rc;
+    } else {
+        launch_square_dist(s, x, dtype, (int)sq.N, (int)lc, dm);
+    }
+    HIPC(hipGetLastError());
+    return 0;
+}
+
 // ---- distances (+ row maxima for the enclosing radius)
 int enqueue_distances(Call& c) {
     const tda_rips_args& a = c.a;
@@ -246,10 +277,7 @@ int enqueue_distances(Call& c) {
                 HIPC(hipMemcpyAsync(B + p.o_x, x, (size_t)L * n * n * c.esz, hipMemcpyHostToDevice, s));
                 x = B + p.o_x;
             }
-            if (p.dtype == TDA_F64)
-                hipLaunchKernelGGL(k_square_dist<double>, dim3(gx, L), dim3(256), 0, s, (const double*)x, n, dist);
-            else
-                hipLaunchKernelGGL(k_square_dist<float>, dim3(gx, L), dim3(256), 0, s, (const float*)x, n, dist);
+            launch_square_dist(s, x, p.dtype, n, L, dist);
         } else {
             const uint64_t ne = binom((uint64_t)n, 2);
             if (ne) HIPC(hipMemcpyAsync(B + p.o_x, x, ne * 4, hipMemcpyHostToDevice, s));

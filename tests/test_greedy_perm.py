@@ -9,6 +9,8 @@ distance-matrix input: over the matrix itself).
 import numpy as np
 import pytest
 
+import side_plan_ref as spr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -127,6 +129,49 @@ def test_batch_layers_do_not_bleed(gpu, oracle):
         check_layer(g, l, M[l], 25, l)
     g32 = gpu.greedy_perm_batch(M.astype(np.float32), 25, distance_matrix=True, want_dperm2all=False)
     assert g32.dperm2all is None and np.array_equal(g32.idx_perm, g.idx_perm) and np.array_equal(g32.lambdas, g.lambdas)
+
+
+# ---- chunks of layers: TDA_SIDE_WS_BYTES caps a chunk's bytes, so that a call of 5 layers runs the chunk loop
+_CHUNK = {}
+
+
+def chunk_case(oracle, form):
+    """(X as the call takes it, its keywords, the plan's keywords, the layers' oracle matrices), once per form."""
+    if form not in _CHUNK:
+        n, d = {"n40_d64": (40, 64), "n150_d64": (150, 64)}.get(form, (65, 3))
+        X = np.stack([cloud(n, d, seed=70 + l) for l in range(5)])
+        dm = np.stack([oracle.distances(X[l]) for l in range(5)])
+        dm.setflags(write=False)
+        plan = dict(L=5, N=n, D=d, dtype=spr.F32, is_dist=False, host_in=True, k=16, want_dp=True)
+        if form == "f64_matrices":
+            _CHUNK[form] = dm.astype(np.float64), dict(distance_matrix=True), dict(plan, D=n, dtype=spr.F64, is_dist=True), dm
+        else:
+            _CHUNK[form] = X, {}, dict(plan, host_in=form != "device_points"), dm
+    return _CHUNK[form]
+
+
+@pytest.mark.parametrize("Lc", [2, 1])
+@pytest.mark.parametrize("form", ["n65_d3", "n40_d64", "n150_d64", "f64_matrices", "device_points"])
+def test_layer_chunks_equal_the_whole_call(gpu, oracle, monkeypatch, form, Lc):
+    """L = 5 in chunks of 2, 2, 1 and of one layer: the chunk buffers and the two kernel events reused,
+    the results at l0 * k, dperm2all copied down per chunk.  D = 64: the partial Grams of a chunk on the
+    whole-layer path (N = 40) and on the tiled path (N = 150); f64 matrices and a device tensor: the chunk's
+    pointer into the caller's memory.  Byte for byte the uncapped call and the host loop on the oracle's matrix."""
+    import torch
+
+    X, kw, plan, dm = chunk_case(oracle, form)
+    Y = torch.from_numpy(X).cuda() if form == "device_points" else X
+    whole = gpu.greedy_perm_batch(Y, 16, **kw)
+    cap = spr.cap_for(spr.greedy, Lc, **plan)
+    assert spr.greedy(cap=cap, **plan)["Lc"] == Lc and spr.greedy(**plan)["Lc"] == 5
+    monkeypatch.setenv("TDA_SIDE_WS_BYTES", str(cap))
+    g = gpu.greedy_perm_batch(Y, 16, **kw)
+    for name in ("idx_perm", "lambdas", "dperm2all"):
+        assert getattr(g, name).tobytes() == getattr(whole, name).tobytes(), name
+    for l in range(5):
+        check_layer(g, l, dm[l], 16, l)
+    print(f"{form} Lc={Lc}: select_ms {g.select_ms:.4f} device_ms {g.device_ms:.4f}")
+    assert 0 < g.select_ms <= g.device_ms
 
 
 def _pairs(res, d):

@@ -51,8 +51,11 @@ def test_perm_constants_match_sources(pkg):
     assert lds_s ** 2 * 8 <= lds_bytes < (lds_s + 1) ** 2 * 8  # the largest tile in the LDS the host asks for
     assert lds_bytes <= 160 * 1024  # of a CU's 160 KiB
     # a launch's rows keep the tiled grid within 65535
-    chunk = re.search(r"constexpr size_t kPermChunkRows = \(size_t\)(\d+) \* kPermR;", host)
+    plan = open(os.path.join(lb.CSRC, "side_plan.h")).read()  # the chunk is part of the host plan; perm_host.h ties kSidePermR to kPermR
+    chunk = re.search(r"constexpr size_t kPermChunkRows = \(size_t\)(\d+) \* kSidePermR;", plan)
     assert int(chunk.group(1)) <= 65535
+    assert int(re.search(r"constexpr int kSidePermR = (\d+);", plan).group(1)) == lb.TDA_PERM_ROWS
+    assert "kSidePermR == kPermR" in host
 
 
 def test_perm_symbols_exported_and_abi_version_unchanged(pkg, built_lib):

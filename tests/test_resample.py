@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import resample_ref as rr
+import side_plan_ref as spr
 
 pytestmark = pytest.mark.gpu
 
@@ -131,6 +132,39 @@ def test_layers_and_resamples_do_not_bleed(gpu):
     per = np.random.default_rng(6).integers(0, n, size=(L, B, 30), dtype=np.int32)
     H_p, H_q = gpu.hausdorff_resamples(X, per), gpu.hausdorff_resamples(X[::-1].copy(), per[::-1].copy())
     assert np.array_equal(H_q, H_p[::-1]) and np.array_equal(H_p, rr.hausdorff(dist_of(gpu, X), per))
+
+
+# ---------------------------------------------------------------- 3b. chunks of layers
+_CHUNK = {}
+
+
+def chunk_case(oracle, n, d):
+    """Five clouds, their oracle matrices (no pipeline call), a shared and a per-layer table: once per shape."""
+    if (n, d) not in _CHUNK:
+        X = clouds(5, n, d, seed=80 + d)
+        dm = np.stack([oracle.distances(X[l]) for l in range(5)])
+        dm.setflags(write=False)
+        rng = np.random.default_rng(n)
+        _CHUNK[n, d] = X, dm, {"shared": rng.integers(0, n, size=(9, 30), dtype=np.int32), "per_layer": rng.integers(0, n, size=(5, 9, 30), dtype=np.int32)}
+    return _CHUNK[n, d]
+
+
+@pytest.mark.parametrize("n,d,table,Lc", [(65, 3, "shared", 2), (65, 3, "shared", 1), (65, 3, "per_layer", 2), (65, 3, "per_layer", 1),
+                                          (150, 64, "per_layer", 2)])
+def test_layer_chunks_equal_the_whole_call(gpu, oracle, monkeypatch, n, d, table, Lc):
+    """L = 5 under a cap of TDA_SIDE_WS_BYTES that serves Lc layers per chunk (2, 2, 1, or one by one): the
+    chunk buffers reused, the results at l0 * B, a per-layer table uploaded chunk by chunk.  Byte for byte
+    the uncapped call and the restatement over the oracle's matrices."""
+    X, dm, tables = chunk_case(oracle, n, d)
+    idx = tables[table]
+    plan = dict(L=5, N=n, D=d, dtype=spr.F32, is_dist=False, host_in=True, B=9, m=30, per_layer_idx=table == "per_layer")
+    whole = gpu.hausdorff_resamples(X, idx)
+    cap = spr.cap_for(spr.resample, Lc, **plan)
+    assert spr.resample(cap=cap, **plan)["Lc"] == Lc and spr.resample(**plan)["Lc"] == 5
+    monkeypatch.setenv("TDA_SIDE_WS_BYTES", str(cap))
+    H = gpu.hausdorff_resamples(X, idx)
+    assert H.shape == (5, 9) and H.tobytes() == whole.tobytes()
+    assert np.array_equal(H, rr.hausdorff(dm, idx))
 
 
 # ---------------------------------------------------------------- 4. input forms
