@@ -301,21 +301,12 @@ int enqueue_h0_large(Call& c) {
     const int n = c.n, L = c.L;
     float* dist = c.dist;
     LayerStats* stats = c.stats;
-    int T = n <= 256 ? 256 : 1024;
-    if (n <= kH0WaveMaxN && !test_env_is("TDA_H0_WAVE", "0")) T = 1024;  // LDS Borůvka: a wave per vertex
-    // best | par | red | sort chunk | (LDS rows) | Borůvka hooks
-    size_t base = 16 + (size_t)n * 8 + (size_t)((n + 1) & ~1) * 4 + 40 * 8 + (size_t)n * 4;
-    base = align_up(base, 16);
-    // n <= kH0WaveMaxN: one-wave Prim on the LDS-staged matrix (sort chunk just covers the forest)
-    const bool wave_ok = !test_env_is("TDA_H0_WAVE", "0");
-    const bool dlds = n <= kH0WaveMaxN && wave_ok;
-    size_t avail = kLdsMax - base - (dlds ? (size_t)4 * n * n : 0);
-    uint64_t ch = 1;
-    if (dlds)
-        ch = next_pow2((uint64_t)n);
-    else
-        while (ch * 2 * 8 <= avail && ch * 2 <= 16384) ch *= 2;
-    size_t lds = base + ch * 8 + (dlds ? (size_t)4 * n * n : 0);
+    // the block size, both LDS carves, the rounds and the elder-rule variant: h0_shape (rips_plan.h)
+    const H0Shape h0 = h0_shape(n);
+    const int T = h0.T;
+    const bool dlds = h0.dlds;
+    const uint64_t ch = h0.ch;
+    const size_t lds = h0.lds;
     if (dlds) {
         hipLaunchKernelGGL((k_h0<kH0WaveQ, true>), dim3(L), dim3(T), lds, s4, dist, n, a.thresh, stats, (uint32_t*)(B + p.o_mst),
                            p.mst_words, (Pair*)(B + p.o_pairs[0]), p.pcap[0], (uint64_t*)(B + p.o_h0s), ilog2(ch),
@@ -327,8 +318,8 @@ int enqueue_h0_large(Call& c) {
     uint64_t* bcheap = (uint64_t*)(B + p.o_bcheap);
     BorCtl* bctl = (BorCtl*)(B + p.o_bctl);
     hipLaunchKernelGGL(k_bor_init, dim3(L), dim3(256), 0, s4, c.rowmax, n, a.thresh, stats, bcomp, bcheap, bctl);
-    const size_t hl = (size_t)((n + 3) & ~3) * 8 + (size_t)n * 8;
-    const int rounds = std::max(1, ilog2(next_pow2((uint64_t)n)));
+    const size_t hl = h0.hl;
+    const int rounds = h0.rounds;
     for (int r = 0; r < rounds; ++r) {
         hipLaunchKernelGGL(k_bor_min, dim3((unsigned)((n + 3) / 4), L), dim3(256), 0, s4, dist, n, stats, bcomp, bcheap, bctl,
                            r == 0 ? 1 : 0);
@@ -341,7 +332,7 @@ int enqueue_h0_large(Call& c) {
     HIPC(hipGetLastError());
     if (int rc = c.tm4.mark("k_bor_rounds")) return rc;
     // elder rule: one wave with register labels up to N = 64 * kH0BorWQ, thread 0 above
-    if (n <= 64 * kH0BorWQ)
+    if (h0.elder == kH0ElderWave)
         hipLaunchKernelGGL((k_h0<kH0BorWQ, false, true>), dim3(L), dim3(T), lds, s4, dist, n, a.thresh, stats,
                            (uint32_t*)(B + p.o_mst), p.mst_words, (Pair*)(B + p.o_pairs[0]), p.pcap[0], (uint64_t*)(B + p.o_h0s),
                            ilog2(ch), (const BorCtl*)bctl);
@@ -383,7 +374,7 @@ int enqueue_side(Call& c) {
         if (int rc = c.tm4.mark("k_h0")) return rc;
     HIPC(hipEventRecord(w.evh, s4));
     if (c.nls) {  // silhouette scores on the same distance matrices (sklearn semantics), after the H0 join
-        const size_t lds = (size_t)c.sil_K * kSilT * 8 + (size_t)n * 4;
+        const size_t lds = silhouette_lds(c.sil_K, n);
         hipLaunchKernelGGL(k_silhouette, dim3(L, c.nls), dim3(kSilT), lds, s4, dist, n, (const int32_t*)w.hsil.dev, c.sil_K,
                            (double*)(w.hsil.dev + c.sil_out_off));
         HIPC(hipGetLastError());
@@ -395,7 +386,7 @@ int enqueue_side(Call& c) {
         // (only without H1: with H1 the main stream joins s2 before the reduction, and
         // TwoNN there would sit on the critical path -- ADVICE r03)
         const bool tn_s2 = !p.dense && p.maxdim == 0;
-        const int pw2 = (int)next_pow2((uint64_t)std::max(n, 64));
+        const int pw2 = twonn_pw2(n);
         hipLaunchKernelGGL(k_twonn, dim3(L), dim3(kTnT), (size_t)pw2 * 4, tn_s2 ? s2 : s4, dist, n, a.twonn_discard, a.twonn_eps, pw2,
                            w.htn.dev);
         HIPC(hipGetLastError());

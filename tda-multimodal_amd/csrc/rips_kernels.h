@@ -841,7 +841,6 @@ __global__ __launch_bounds__(1024) void k_bor_hook(int n, int32_t* __restrict__ 
 }
 
 constexpr int kH0WaveQ = (kH0WaveMaxN + 63) / 64;
-constexpr int kH0BorWQ = 16;  // Borůvka path: one-wave elder rule with register labels up to N = 1024
 template <int WQ, bool LROWS, bool BOR = false>
 __global__ __launch_bounds__(1024) void k_h0(const float* __restrict__ dist, int n, float user_thresh,
                                              LayerStats* __restrict__ stats, uint32_t* __restrict__ mst_bits,
@@ -1957,8 +1956,7 @@ __global__ __launch_bounds__(1024) void k_emit(LayerStats* __restrict__ stats, i
 // One block per (layer, label set); thread per point i, j-major loop over
 // column i of the symmetric matrix (D[j][i]), so a wave's loads are coalesced.
 // labels: [S][N] codes 0..K-1, every code present (checked on the host).
-constexpr int kSilT = 256;
-constexpr int kSilMaxK = 32;
+// (kSilT points per pass, kSilMaxK clusters at most: rips_shapes.h)
 __global__ __launch_bounds__(kSilT) void k_silhouette(const float* __restrict__ dist, int n, const int32_t* __restrict__ labels,
                                                       int K, double* __restrict__ out) {
     extern __shared__ __align__(16) unsigned char sil_lds[];
@@ -2029,7 +2027,7 @@ __global__ __launch_bounds__(kSilT) void k_silhouette(const float* __restrict__ 
 // off-diagonal distances (lane-strided, coalesced, DPP top-2 merge), the
 // finite ratios go to LDS, a bitonic sort orders them, block reductions do
 // the regression.  LDS: next_pow2(n) floats (n <= 8192).
-constexpr int kTnT = 1024;
+// (kTnT threads: rips_shapes.h)
 __device__ __forceinline__ void top2_insert(float v, float& a, float& b) {
     if (v < a) {
         b = a;

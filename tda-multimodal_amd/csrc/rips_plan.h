@@ -121,6 +121,51 @@ inline ReduceAllCfg reduce_cfg(int n, int maxdim, const uint64_t* piv_words, boo
     return c;
 }
 
+// H0 of kSmallN < n (enqueue_h0_large, rips_enqueue.h): the block size, the LDS carve of k_h0 and
+// of k_bor_hook, the Borůvka rounds and which k_h0 instantiation runs the elder rule.
+// k_h0's LDS: 16 | best n x 8 | par n (even) x 4 | red 40 x 8 | hooks n x 4, rounded up to 16 (base),
+// then the sort chunk ch x 8 and, up to kH0WaveMaxN, the layer's matrix 4 n^2 (dlds).  ch is the
+// largest power of two that fits beside base, 16384 at most: block_sort merges in HBM once the
+// forest's n - 1 keys outgrow it.
+enum { kH0ElderLds = 0, kH0ElderWave = 1, kH0ElderSerial = 2 };
+struct H0Shape {
+    int T = 0;          // threads of the k_h0 block
+    size_t base = 0;    // k_h0's LDS in front of the sort chunk
+    bool dlds = false;  // n <= kH0WaveMaxN: k_h0<kH0WaveQ, true> alone, the matrix staged in LDS
+    uint64_t ch = 0;    // keys of the LDS sort chunk (a power of two: the kernel gets ilog2(ch))
+    size_t lds = 0;     // dynamic LDS of the k_h0 launch
+    size_t hl = 0;      // dynamic LDS of k_bor_hook (not launched when dlds)
+    int rounds = 0;     // (k_bor_min, k_bor_hook) rounds
+    int elder = 0;      // kH0ElderLds: k_h0<kH0WaveQ, true>; Wave: k_h0<kH0BorWQ, false, true>; Serial: k_h0<0, false, true>
+};
+inline H0Shape h0_shape(int n) {
+    H0Shape h;
+    h.T = n <= 256 ? 256 : 1024;
+    if (n <= kH0WaveMaxN && !test_env_is("TDA_H0_WAVE", "0")) h.T = 1024;  // LDS Borůvka: a wave per vertex
+    // best | par | red | sort chunk | (LDS rows) | Borůvka hooks
+    h.base = 16 + (size_t)n * 8 + (size_t)((n + 1) & ~1) * 4 + 40 * 8 + (size_t)n * 4;
+    h.base = align_up(h.base, 16);
+    // n <= kH0WaveMaxN: one-wave Prim on the LDS-staged matrix (sort chunk just covers the forest)
+    const bool wave_ok = !test_env_is("TDA_H0_WAVE", "0");
+    h.dlds = n <= kH0WaveMaxN && wave_ok;
+    const size_t avail = kLdsMax - h.base - (h.dlds ? (size_t)4 * n * n : 0);
+    h.ch = 1;
+    if (h.dlds)
+        h.ch = next_pow2((uint64_t)n);
+    else
+        while (h.ch * 2 * 8 <= avail && h.ch * 2 <= 16384) h.ch *= 2;
+    h.lds = h.base + h.ch * 8 + (h.dlds ? (size_t)4 * n * n : 0);
+    h.hl = (size_t)((n + 3) & ~3) * 8 + (size_t)n * 8;
+    h.rounds = std::max(1, ilog2(next_pow2((uint64_t)n)));
+    // elder rule: one wave with register labels up to N = 64 * kH0BorWQ, thread 0 above
+    h.elder = h.dlds ? kH0ElderLds : n <= 64 * kH0BorWQ ? kH0ElderWave : kH0ElderSerial;
+    return h;
+}
+// the side metrics' dynamic LDS: k_twonn sorts next_pow2(max(n, 64)) floats, k_silhouette keeps
+// K x kSilT f64 sums and the n labels
+inline int twonn_pw2(int n) { return (int)next_pow2((uint64_t)std::max(n, 64)); }
+inline size_t silhouette_lds(int K, int n) { return (size_t)K * kSilT * 8 + (size_t)n * 4; }
+
 // Which kernels turn (N, D) point clouds into distances (launch_point_distances, rips_enqueue.h):
 // the scalar k_distance, or from D = kDistMfmaMinD up the FP64 MFMA Gram tiles, as K slices
 // (dsplit > 1: partial Grams + k_distance_combine) when the tiles alone leave CUs idle: aim at

@@ -79,6 +79,15 @@ struct BorCtl {
     uint32_t done, pad;
 };
 constexpr int kH0WaveMaxN = 190;  // 4 n^2 B of LDS staging
+constexpr int kH0BorWQ = 16;      // Borůvka path: one-wave elder rule with register labels up to N = 1024
+constexpr int kBorHookLdsMax = 150 * 1024;  // k_bor_hook's dynamic LDS attribute
+
+// ---------------------------------------------------------------- side metrics (rips_kernels.h)
+constexpr int kSilT = 256;     // k_silhouette: points per pass (threads of a block)
+constexpr int kSilMaxK = 32;   // k_silhouette: clusters of a label set at most
+constexpr int kSilLdsMax = 128 * 1024;  // k_silhouette's dynamic LDS attribute
+constexpr int kTnT = 1024;     // k_twonn: threads of a block
+constexpr int kTnLdsMax = 8192 * 4;     // k_twonn's dynamic LDS attribute
 
 // ---------------------------------------------------------------- one wave per layer (rips_reduce.h)
 struct Reduce2Cfg {  // per-dim LDS carve, decided on the host

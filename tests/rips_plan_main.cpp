@@ -7,6 +7,7 @@
 // test knobs are read from the environment, as in the library.  make_plan runs twice per case and
 // the program fails (exit 3) if the two plans differ in any printed field.  The knobs that are no
 // field of a Plan go to stderr, one line: step_limit, par_step_limit(1), par_step_limit(2), par_pool_shift.
+// With the arguments `h0 LO HI` it prints the H0 shape (h0_shape) of every N in LO .. HI instead.
 #include <cstdio>
 #include <string>
 
@@ -53,7 +54,23 @@ static std::string print(const Plan& p) {
     return out;
 }
 
-int main() {
+// `h0 LO HI` as arguments: no plans; one line of the limits the H0 and side-metric launches are held to,
+// then for every N in LO .. HI the H0 shape (h0_shape) and the side metrics' dynamic LDS, as name=value
+static int h0_scan(int lo, int hi) {
+    printf("limits kLdsMax=%d kBorHookLdsMax=%d kTnLdsMax=%d kSilLdsMax=%d kSilMaxK=%d kSilT=%d kTnT=%d kH0BorWQ=%d kH0WaveMaxN=%d\n", kLdsMax,
+           kBorHookLdsMax, kTnLdsMax, kSilLdsMax, kSilMaxK, kSilT, kTnT, kH0BorWQ, kH0WaveMaxN);
+    for (int n = lo; n <= hi; ++n) {
+        const H0Shape h = h0_shape(n), again = h0_shape(n);
+        if (h.T != again.T || h.base != again.base || h.ch != again.ch || h.lds != again.lds || h.hl != again.hl || h.elder != again.elder) return 3;
+        printf("N=%d T=%d base=%zu dlds=%d ch=%llu chunk_log2=%d lds=%zu hl=%zu rounds=%d elder=%d pw2=%d tn_lds=%zu sil_lds=%zu\n", n, h.T, h.base,
+               (int)h.dlds, (unsigned long long)h.ch, ilog2(h.ch), h.lds, h.hl, h.rounds, h.elder, twonn_pw2(n), (size_t)twonn_pw2(n) * 4,
+               silhouette_lds(kSilMaxK, n));
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 4 && std::string(argv[1]) == "h0") return h0_scan(atoi(argv[2]), atoi(argv[3]));
     printf("sizeof Pair=%zu LayerStats=%zu BorCtl=%zu ParCtl=%zu kLdsMax=%d kDenseMaxN=%d\n", sizeof(Pair), sizeof(LayerStats), sizeof(BorCtl),
            sizeof(ParCtl), kLdsMax, kDenseMaxN);
     fprintf(stderr, "knobs step_limit=%llu par_steps_h1=%llu par_steps_h2=%llu par_pool_shift=%d\n", (unsigned long long)step_limit(),

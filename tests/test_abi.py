@@ -86,6 +86,30 @@ def test_invalid_arguments_rejected_before_device(pkg, built_lib):
                          ctypes.byref(res)) == -2  # cocycles
 
 
+def test_size_limits_refused_before_device(pkg, built_lib):
+    """The point-count limits of tda_rips_batch: 8192 for any maxdim, 2900 for H1 (a key holds a 32-bit
+    row-simplex index and C(2900, 3) < 2^32), 2048 for H2.  One past each is
+    TDA_E_UNSUPPORTED with the limit in the message, before any device work (the calls at the limits
+    themselves run in tests/test_large_n.py)."""
+    import math
+
+    assert 2 ** 31 < math.comb(2900, 3) < 2 ** 32
+    L = pkg.lib()
+    _lib = pkg._lib
+    res = ctypes.POINTER(_lib.RipsResult)()
+    X = np.zeros((1, 8193, 3), np.float32)
+
+    def call(n, maxdim):
+        a = _lib.RipsArgs()
+        a.x, a.dtype, a.L, a.N, a.D, a.maxdim, a.modulus = X.ctypes.data, 0, 1, n, 3, maxdim, 2
+        a.thresh = float("inf")
+        return L.tda_rips_batch(ctypes.byref(a), ctypes.byref(res)), L.tda_last_error()
+
+    for n, maxdim, limit in ((2901, 1, b"2900"), (2049, 2, b"2048"), (8193, 0, b"8192"), (8193, 1, b"8192"), (8193, 2, b"8192")):
+        rc, msg = call(n, maxdim)
+        assert rc == -2 and limit in msg, (n, maxdim, rc, msg)  # TDA_E_UNSUPPORTED
+
+
 def test_product_path_does_not_reference_oracle():
     pkgdir = os.path.join(ROOT, "tda-multimodal_amd")
     for dp, _, fs in os.walk(pkgdir):

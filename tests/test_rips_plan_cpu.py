@@ -15,7 +15,10 @@ undefined-behaviour sanitizers and run as a program of its own, once per environ
   TDA_PAR_STEPS_H1 / _H2 set the step limit of one k_reduce_par launch and leave step_limit() alone;
 * the size borders of tests/size_borders.py, which tests/test_size_borders.py runs on a device: the
   plan changes kernel, instantiation, LDS layout or key format at exactly the N listed there (the
-  dense borders are in this test and not in the pin's NS: the pin would outgrow its size rule).
+  dense borders are in this test and not in the pin's NS: the pin would outgrow its size rule);
+* the H0 shape (h0_shape: block size, LDS carves, sort chunk, Borůvka rounds, elder-rule variant) of every
+  N = 65 .. 8192 against tests/large_n.py, which tests/test_large_n.py runs on a device, and the dynamic LDS
+  of k_h0, k_bor_hook, k_twonn and k_silhouette against their limits at every N.
 """
 import math
 import os
@@ -25,6 +28,7 @@ import sys
 
 import pytest
 
+import large_n as ln
 import size_borders as sb
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -404,6 +408,80 @@ def test_size_borders_forced_variants(exe):
         # in csrc/rips.hip), so on a device such a call can replay the two-wave graph of the default
         # call of its shape: the GPU file has no TDA_P1_WAVES case (left out)
         assert {k for k in q if q[k] != p[k]} == {"p1_waves", "p1_lds"}, c
+
+
+# ---- the H0 shape above the dense path and the side metrics' LDS (tests/large_n.py, run by tests/test_large_n.py)
+def h0_scan(exe, lo, hi):
+    """-> (the limits line, {N: fields}) of `<program> h0 lo hi`"""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("TDA_")}
+    lines = subprocess.run([exe, "h0", str(lo), str(hi)], capture_output=True, text=True, check=True, env=env).stdout.splitlines()
+    rows = [dict((k, int(v)) for k, v in (t.split("=") for t in ln_.split())) for ln_ in lines[1:]]
+    assert [r["N"] for r in rows] == list(range(lo, hi + 1))
+    return dict((k, int(v)) for k, v in (t.split("=") for t in lines[0].split()[1:])), {r["N"]: r for r in rows}
+
+
+def test_large_n_h0_borders_are_where_the_shape_changes(exe):
+    """Every N in 66 .. 8192 at which h0_shape changes a field of H0_FIELDS is a border of H0_BORDERS, with
+    the values on both sides named there, and the other way round.  A moved constant fails here, and the
+    message says where the shape changes now: the sizes tests/large_n.py, and through it the GPU file,
+    must move to."""
+    lo, hi = ln.H0_SCAN
+    assert (lo, hi) == (K_DENSE_MAX_N + 1, ln.MAX_N)
+    _, rows = h0_scan(exe, lo, hi)
+    found = []
+    for n in range(lo + 1, hi + 1):
+        diff = {k: (rows[n - 1][k], rows[n][k]) for k in ln.H0_FIELDS if rows[n - 1][k] != rows[n][k]}
+        if diff:
+            found.append((n, diff))
+    want = [(n, {k: v for k, v in f.items() if k in ln.H0_FIELDS}) for n, f in ln.H0_BORDERS]
+    fd, wd = dict(found), dict(want)
+    assert found == want, "the H0 shape changes at N = %s, tests/large_n.py says %s; move these:\n%s" % (
+        [n for n, _ in found], [n for n, _ in want],
+        "\n".join("  N = %d: the shape changes %r, the file says %r" % (n, fd.get(n), wd.get(n)) for n in sorted(set(fd) | set(wd)) if fd.get(n) != wd.get(n)))
+    for n, f in ln.H0_BORDERS:
+        assert (rows[n - 1]["lds"], rows[n]["lds"]) == f["lds"], (n, "lds")
+        assert ln.h0_below(n) == {k: rows[n - 1][k] for k in ln.H0_FIELDS}, n
+    # the sizes that follow from H0_BORDERS, restated: after H0_BORDERS has moved this literal moves too
+    assert ln.H0_NS == (1024, 1025, 2026, 2027, 4096, 4097, 4098, 6122, 6123, 8170, 8171, 8191, 8192), \
+        "derived from H0_BORDERS; if H0_BORDERS was moved on purpose, restate this literal here"
+    # the chunk is a power of two, what the kernel is told (ilog2) is that chunk, and the merge passes of block_sort
+    # (more keys than the chunk) run exactly where tests/large_n.py says: two chunks from 6123, four from 8171
+    for n, r in rows.items():
+        assert r["ch"] == 1 << r["chunk_log2"] and r["rounds"] == max(1, (n - 1).bit_length()), n
+        chunks = -(-(n - 1) // r["ch"])
+        assert chunks == (1 if n <= 6122 else 2 if n <= 8170 else 4), (n, chunks)
+    assert {c[0] for c in ln.H0_THRESH_CASES} == {6122, 6123}
+
+
+def test_large_n_lds_fits_at_every_n(exe):
+    """The dynamic LDS of the four launches that grow with N, at every N = 65 .. 8192, against the limits
+    restated here from the attributes csrc/rips.hip sets (init_device): a moved constant, or a carve that
+    grew, fails and names the N."""
+    limits, rows = h0_scan(exe, *ln.H0_SCAN)
+    assert limits == dict(kLdsMax=160 * 1024, kBorHookLdsMax=150 * 1024, kTnLdsMax=8192 * 4, kSilLdsMax=128 * 1024, kSilMaxK=32, kSilT=256,
+                          kTnT=1024, kH0BorWQ=16, kH0WaveMaxN=190)
+    assert (ln.K_LDS_MAX, ln.BOR_HOOK_LDS_MAX, ln.TWONN_LDS_MAX, ln.SIL_LDS_MAX, ln.SIL_MAX_K, ln.SIL_T, ln.TWONN_T) == \
+        (160 * 1024, 150 * 1024, 8192 * 4, 128 * 1024, 32, 256, 1024)
+    for n, r in rows.items():
+        # k_h0: 16 | best n x 8 | par n (even) x 4 | red 40 x 8 | hooks n x 4, rounded up to 16; the chunk; the staged matrix
+        base = (16 + 8 * n + 4 * ((n + 1) & ~1) + 320 + 4 * n + 15) // 16 * 16
+        assert r["base"] == base and r["lds"] == base + 8 * r["ch"] + (4 * n * n if r["dlds"] else 0), n
+        assert r["lds"] <= K_LDS_MAX, "k_h0 at N = %d: %d bytes of LDS" % (n, r["lds"])
+        # the chunk is the largest that fits (no staged matrix), 16384 keys at most
+        if not r["dlds"]:
+            assert r["ch"] == 16384 or base + 16 * r["ch"] > K_LDS_MAX, n
+        else:
+            assert r["ch"] >= n - 1, n  # the LDS path never merges
+        assert r["hl"] == 8 * ((n + 3) & ~3) + 8 * n, n
+        assert r["hl"] <= 150 * 1024, "k_bor_hook at N = %d: %d bytes of LDS" % (n, r["hl"])
+        assert r["pw2"] >= max(n, 64) and r["pw2"] & (r["pw2"] - 1) == 0 and r["pw2"] < 2 * max(n, 64) and r["tn_lds"] == 4 * r["pw2"], n
+        assert r["pw2"] * 4 <= 8192 * 4, "k_twonn at N = %d: %d bytes of LDS" % (n, r["tn_lds"])
+        assert r["sil_lds"] == 32 * 2048 + 4 * n, n
+        assert 32 * 2048 + 4 * n <= 128 * 1024, "k_silhouette at N = %d: %d bytes of LDS" % (n, r["sil_lds"])
+    top = rows[ln.MAX_N]
+    assert (top["lds"], top["hl"], top["sil_lds"], top["tn_lds"]) == (ln.H0_LDS_AT_8192, ln.BOR_HOOK_LDS_AT_8192, ln.SIL_LDS_AT_8192, ln.TWONN_LDS_MAX)
+    # k_twonn's strided loops take pw2 / kTnT trips: one up to n = 1024, eight at 8192 -- the sizes the GPU file runs
+    assert [rows[n]["pw2"] // 1024 for n in ln.TWONN_NS] == [1, 1, 2, 2, 4, 8, 8]
 
 
 if __name__ == "__main__":
