@@ -354,6 +354,86 @@ int tda_resample(const tda_resample_args *args, tda_resample_result **out);
 void tda_resample_free(tda_resample_result *r);
 
 /*
+ * H0 persistence of subsamples of L layers on the GPU: the device stage of the
+ * persistent-homology dimension (Adams et al. 2020; Birdal et al. 2021).  The
+ * H0 deaths of a subsample are the edge weights of the minimum spanning tree
+ * of its points; E_alpha is the sum of their alpha-th powers.
+ * Per layer l, dm is the matrix of tda_resample: the library's own f32
+ * distances, symmetric with a zero diagonal (the sklearn-exact kernels for f32
+ * points; for distance-matrix input the upper triangle).  Subsample b has
+ * s = sizes[b] positions, 1 <= s <= m; position j holds the point
+ * p_j = idx[b][j] (repeats allowed; entries from sizes[b] on are never read).
+ * With W[i][j] = dm[l][p_i][p_j], Prim started at position 0:
+ *     the tree is {0}, key[j] = W[0][j]
+ *     for t = 1 .. s-1:
+ *         j* = the position outside the tree with the smallest key
+ *              (comparisons are `<`; among equal keys the LOWEST position)
+ *         death[b][t-1] = key[j*]
+ *         acc += term(key[j*])
+ *         j* joins the tree
+ *         key[j] = W[j*][j] wherever that is < key[j]
+ * acc is a double that starts at 0.0 and is added to sequentially in step
+ * order (one lane owns it; the sum is never reduced in parallel).  term(w) is
+ * (double)w for alpha == 1, (double)w * (double)w for alpha == 2 and
+ * pow((double)w, alpha) for any other alpha.  E[l][b] = acc; for s == 1 it is
+ * 0.0 and there are no deaths.
+ * What follows: every death is an f32 value of dm, copied and compared, never
+ * computed.  For alpha 1 and 2 every term is exact in f64 and the order of the
+ * additions is fixed, so E equals a sequential numpy loop bit for bit.  For
+ * another alpha the terms differ from another library's pow by the two
+ * roundings; every term is non-negative, so the sum is within
+ * (s + 16) * 2^-52 relative of that loop.  The sorted deaths are the finite H0
+ * deaths of ripser on the subsample: the multiset of MST weights is unique,
+ * the lowest-position rule only fixes the order of the deaths and of the sum.
+ * Non-finite distances: the Python binding refuses host input that holds
+ * them; device input is not checked, the result for it is unspecified, and
+ * the kernel still terminates and stays in bounds (the argmin is a 64-bit
+ * minimum over (ordered key bits, position): a position is always chosen).
+ * The call is of the resampling family: it runs on tda_resample's stream and
+ * workspace (it adds neither to the process), captures no graph, and
+ * synchronises before it returns.  The workspace holds the distance stage of
+ * Lc layers at a time (as tda_resample; a table per layer and the deaths count
+ * in), and beside that, whole, E (L * B * 8 bytes), sizes and a shared table.
+ * Checked on the host before any device work, in this order: a NULL pointer,
+ * L, N, D < 1 or a bad dtype, B < 1, m < 1, a sizes[b] outside [1, m], an
+ * index outside [0, N) among the first sizes[b] entries of a row, alpha not
+ * finite or <= 0: TDA_E_INVALID.  N > 8192, m > 8192, L * B > 2^27,
+ * want_deaths with L * B * (m - 1) > 2^27, float64 POINT clouds:
+ * TDA_E_UNSUPPORTED.
+ * Added to ABI 8 (new symbols only; no existing struct changed).
+ */
+#define TDA_SH0_MAX_OUT (1ll << 27)
+
+typedef struct tda_subsample_h0_args {
+    const void *x;          /* (L, N, D) points or (L, N, N) distances, host or device */
+    int32_t dtype;          /* TDA_F32 | TDA_F64 (TDA_F64: distance matrices only)  */
+    int32_t x_on_device;    /* 1: x is a device pointer on `device`                 */
+    int64_t L, N, D;        /* D ignored when is_dist                               */
+    int32_t is_dist;        /* 1: x holds (L, N, N) distance matrices (upper used)  */
+    int32_t device;         /* HIP device ordinal                                   */
+    void *stream;           /* device input is read after it; NULL = null stream    */
+    int64_t B;              /* subsamples per layer, >= 1                           */
+    int32_t m;              /* the table's row length, 1 .. 8192                    */
+    int32_t idx_per_layer;  /* 0: idx is (B, m), shared by every layer; 1: (L, B, m) */
+    const int32_t *idx;     /* HOST indices into 0 .. N-1                           */
+    const int32_t *sizes;   /* HOST [B], shared by all layers: 1 <= sizes[b] <= m   */
+    double alpha;           /* the power of a death in E: finite, > 0               */
+    int32_t want_deaths;    /* 1: return the deaths too                             */
+} tda_subsample_h0_args;
+
+typedef struct tda_subsample_h0_result {
+    int64_t L, N, B, m;
+    const double *E;        /* host [L][B]                                          */
+    const float *deaths;    /* host [L][B][m-1] in step order when want_deaths,
+                               entries from sizes[b]-1 on are 0; else NULL          */
+    int32_t device;
+    double device_ms;       /* device time of the call (HIP events)                 */
+} tda_subsample_h0_result;
+
+int tda_subsample_h0(const tda_subsample_h0_args *args, tda_subsample_h0_result **out);
+void tda_subsample_h0_free(tda_subsample_h0_result *r);
+
+/*
  * The permutation test between groups of diagrams (Robinson and Turner 2017,
  * "Hypothesis testing for topological data analysis") on the GPU.  Inputs, all
  * on the host: w, an (S, S) float64 matrix of the q-th powers of the pairwise

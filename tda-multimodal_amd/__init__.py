@@ -7,16 +7,17 @@ include/tda_rips.h; no CPU fallback.
 """
 import sys as _sys
 
-from . import bootstrap, diagrams, distributed, hypothesis, metrics, synthetic, umap  # noqa: F401
+from . import bootstrap, diagrams, distributed, hypothesis, metrics, phdim, synthetic, umap  # noqa: F401
 from .bootstrap import ConfidenceBands, confidence_bands, hausdorff_resamples, resample_indices  # noqa: F401
 from .diagrams import (betti_curve, betti_curves, bottleneck, bottleneck_matrix, entropy_curve, entropy_curves, fisher,  # noqa: F401
                        fisher_kernel_matrix, fisher_matrix, heat, heat_kernel_matrix, heat_matrix, lifespan_curve, lifespan_curves, persistence_curves, persistence_image, persistence_images,
                        persistence_landscape, persistence_landscapes, persistence_silhouette, persistence_silhouettes, sliced_wasserstein,
                        sliced_wasserstein_kernel, sliced_wasserstein_matrix, wasserstein, wasserstein_matrix)
+from .phdim import PHDimension, h0_subsamples, ph_dimension, subsample_indices  # noqa: F401
 from .hypothesis import PermutationTest, diagram_permutation_test, label_permutations, permutation_test  # noqa: F401
 from .metrics import (compute_effective_dimensionality, compute_fixed_window_ed, compute_fixed_window_id,  # noqa: F401
                       compute_intrinsic_dimensionality, matrix_entropy, matrix_entropy_profile)
-from ._lib import BOTTLENECK_EXPORTS, CURVE_EXPORTS, DGM_EXPORTS, EXPORTS, FISHER_EXPORTS, HEAT_EXPORTS, LIB_PATH, VECTOR_EXPORTS, WASSERSTEIN_EXPORTS, build, lib  # noqa: F401
+from ._lib import BOTTLENECK_EXPORTS, CURVE_EXPORTS, DGM_EXPORTS, EXPORTS, FISHER_EXPORTS, HEAT_EXPORTS, LIB_PATH, SUBSAMPLE_H0_EXPORTS, VECTOR_EXPORTS, WASSERSTEIN_EXPORTS, build, lib  # noqa: F401
 from .pipeline import (get_max_persistence, get_persistence, layer_distance_matrix, layer_features, layer_record,  # noqa: F401
                        layer_record_adversarial, peak_layer, run_adversarial_condition, run_sweep, write_layer_stats,
                        write_summary_stats)
@@ -63,6 +64,10 @@ __all__ = [
     "ConfidenceBands",
     "resample_indices",
     "hausdorff_resamples",
+    "ph_dimension",
+    "PHDimension",
+    "h0_subsamples",
+    "subsample_indices",
     "permutation_test",
     "diagram_permutation_test",
     "label_permutations",

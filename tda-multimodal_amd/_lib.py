@@ -219,6 +219,40 @@ class ResampleResult(ctypes.Structure):  # include/tda_rips.h tda_resample_resul
     ]
 
 
+class SubsampleH0Args(ctypes.Structure):  # include/tda_rips.h tda_subsample_h0_args
+    _fields_ = [
+        ("x", ctypes.c_void_p),
+        ("dtype", ctypes.c_int32),
+        ("x_on_device", ctypes.c_int32),
+        ("L", ctypes.c_int64),
+        ("N", ctypes.c_int64),
+        ("D", ctypes.c_int64),
+        ("is_dist", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("stream", ctypes.c_void_p),
+        ("B", ctypes.c_int64),
+        ("m", ctypes.c_int32),
+        ("idx_per_layer", ctypes.c_int32),
+        ("idx", ctypes.c_void_p),  # host int32 (B, m), or (L, B, m) with idx_per_layer
+        ("sizes", ctypes.c_void_p),  # host int32 (B,)
+        ("alpha", ctypes.c_double),
+        ("want_deaths", ctypes.c_int32),
+    ]
+
+
+class SubsampleH0Result(ctypes.Structure):  # include/tda_rips.h tda_subsample_h0_result
+    _fields_ = [
+        ("L", ctypes.c_int64),
+        ("N", ctypes.c_int64),
+        ("B", ctypes.c_int64),
+        ("m", ctypes.c_int64),
+        ("E", ctypes.POINTER(ctypes.c_double)),
+        ("deaths", _f32p),
+        ("device", ctypes.c_int32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
 class PermArgs(ctypes.Structure):  # include/tda_rips.h tda_perm_args
     _fields_ = [
         ("w", ctypes.c_void_p),  # host float64 (S, S)
@@ -253,6 +287,9 @@ TDA_PERM_ROWS = 8  # csrc/perm_kernels.h kPermR: labellings of one k_perm_tiled 
 TDA_RS_LDS_N = 128  # csrc/resample_kernels.h kRsLdsN: the largest N whose matrix k_resample_hausdorff stages in LDS
 TDA_RS_MAX_POINTS = 8192  # N and m of a tda_resample call
 TDA_RESAMPLE_MAX_OUT = 1 << 27  # resamples (L * B) of one call
+TDA_SH0_MAX_OUT = 1 << 27  # subsamples (L * B), and deaths (L * B * (m - 1)), of one tda_subsample_h0 call
+TDA_SH0_LDS_N = 128  # csrc/sh0_kernels.h kSh0LdsN: the largest N whose matrix k_subsample_h0 stages in LDS
+TDA_SH0_LDS_M = 128  # csrc/sh0_kernels.h kSh0LdsM: the largest row length of that path
 
 
 class SwArgs(ctypes.Structure):  # include/tda_dgm.h tda_sw_args
@@ -525,6 +562,8 @@ VECTOR_EXPORTS = DGM_ENTRIES["pl"][:2] + DGM_ENTRIES["pi"][:2]
 HEAT_EXPORTS = DGM_ENTRIES["hk"][:2]
 CURVE_EXPORTS = DGM_ENTRIES["pc"][:2]
 FISHER_EXPORTS = DGM_ENTRIES["pf"][:2]
+# include/tda_rips.h again: the subsample H0 entry (its names hold a digit, so they have a tuple of their own)
+SUBSAMPLE_H0_EXPORTS = ("tda_subsample_h0", "tda_subsample_h0_free")
 
 _lib = None
 
@@ -653,6 +692,10 @@ def lib():
     L.tda_resample.restype = ctypes.c_int
     L.tda_resample_free.argtypes = [ctypes.POINTER(ResampleResult)]
     L.tda_resample_free.restype = None
+    L.tda_subsample_h0.argtypes = [ctypes.POINTER(SubsampleH0Args), ctypes.POINTER(ctypes.POINTER(SubsampleH0Result))]
+    L.tda_subsample_h0.restype = ctypes.c_int
+    L.tda_subsample_h0_free.argtypes = [ctypes.POINTER(SubsampleH0Result)]
+    L.tda_subsample_h0_free.restype = None
     L.tda_permutation_test.argtypes = [ctypes.POINTER(PermArgs), ctypes.POINTER(ctypes.POINTER(PermResult))]
     L.tda_permutation_test.restype = ctypes.c_int
     L.tda_perm_free.argtypes = [ctypes.POINTER(PermResult)]

@@ -1237,6 +1237,8 @@ void tda_pipe_destroy(tda_pipe* pipe) { delete pipe; }
 #include "greedy_host.h"
 // resamples of a layer for bootstrap confidence bands (include/tda_rips.h tda_resample)
 #include "resample_host.h"
+// H0 persistence of subsamples for the persistent-homology dimension (include/tda_rips.h tda_subsample_h0)
+#include "sh0_host.h"
 // the permutation test between groups of diagrams (include/tda_rips.h tda_permutation_test)
 #include "perm_host.h"
 // sliced Wasserstein distances between persistence diagrams (include/tda_dgm.h)
