@@ -8,6 +8,7 @@ result objects) is the small CPython extension _hostviews.so, required too.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -565,6 +566,15 @@ FISHER_EXPORTS = DGM_ENTRIES["pf"][:2]
 # include/tda_rips.h again: the subsample H0 entry (its names hold a digit, so they have a tuple of their own)
 SUBSAMPLE_H0_EXPORTS = ("tda_subsample_h0", "tda_subsample_h0_free")
 
+# include/tda_rips.h again: the side entries of the same shape, int entry(const args*, result**) and void free(result*)
+SIDE_ENTRIES = {
+    "greedy": ("tda_greedy_perm", "tda_greedy_free", GreedyArgs, GreedyResult),
+    "resample": ("tda_resample", "tda_resample_free", ResampleArgs, ResampleResult),
+    "sh0": SUBSAMPLE_H0_EXPORTS + (SubsampleH0Args, SubsampleH0Result),
+    "perm": ("tda_permutation_test", "tda_perm_free", PermArgs, PermResult),
+}
+_ENTRIES = {**DGM_ENTRIES, **SIDE_ENTRIES}
+
 _lib = None
 
 
@@ -684,22 +694,6 @@ def lib():
     L.tda_effective_dim_windows.restype = ctypes.c_int
     L.tda_matrix_entropy.argtypes = [ctypes.POINTER(SpectralArgs), _f32p]
     L.tda_matrix_entropy.restype = ctypes.c_int
-    L.tda_greedy_perm.argtypes = [ctypes.POINTER(GreedyArgs), ctypes.POINTER(ctypes.POINTER(GreedyResult))]
-    L.tda_greedy_perm.restype = ctypes.c_int
-    L.tda_greedy_free.argtypes = [ctypes.POINTER(GreedyResult)]
-    L.tda_greedy_free.restype = None
-    L.tda_resample.argtypes = [ctypes.POINTER(ResampleArgs), ctypes.POINTER(ctypes.POINTER(ResampleResult))]
-    L.tda_resample.restype = ctypes.c_int
-    L.tda_resample_free.argtypes = [ctypes.POINTER(ResampleResult)]
-    L.tda_resample_free.restype = None
-    L.tda_subsample_h0.argtypes = [ctypes.POINTER(SubsampleH0Args), ctypes.POINTER(ctypes.POINTER(SubsampleH0Result))]
-    L.tda_subsample_h0.restype = ctypes.c_int
-    L.tda_subsample_h0_free.argtypes = [ctypes.POINTER(SubsampleH0Result)]
-    L.tda_subsample_h0_free.restype = None
-    L.tda_permutation_test.argtypes = [ctypes.POINTER(PermArgs), ctypes.POINTER(ctypes.POINTER(PermResult))]
-    L.tda_permutation_test.restype = ctypes.c_int
-    L.tda_perm_free.argtypes = [ctypes.POINTER(PermResult)]
-    L.tda_perm_free.restype = None
     L.tda_umap_transform.argtypes = [ctypes.POINTER(UmapTransformArgs)]
     L.tda_umap_transform.restype = ctypes.c_int
     # the native sweep pipeline (tda_pipe_*): the pipe is an opaque handle, tickets and call ids are uint64
@@ -718,7 +712,7 @@ def lib():
     L.tda_pipe_release.restype = ctypes.c_int
     L.tda_pipe_destroy.argtypes = [ctypes.c_void_p]
     L.tda_pipe_destroy.restype = None
-    for entry, free, Args, Result in DGM_ENTRIES.values():
+    for entry, free, Args, Result in _ENTRIES.values():
         getattr(L, entry).argtypes = [ctypes.POINTER(Args), ctypes.POINTER(ctypes.POINTER(Result))]
         getattr(L, entry).restype = ctypes.c_int
         getattr(L, free).argtypes = [ctypes.POINTER(Result)]
@@ -731,3 +725,18 @@ def check(rc: int) -> None:
     if rc != 0:
         msg = lib().tda_last_error().decode(errors="replace")
         raise ERRORS.get(rc, RuntimeError)(msg)
+
+
+@contextlib.contextmanager
+def result(entry: str, args):
+    """One call of a result-returning entry (a key of DGM_ENTRIES or SIDE_ENTRIES): the return code
+    checked, the library-owned result struct yielded and freed on exit.  What outlives the block
+    must be copied inside it."""
+    symbol, free, _, Result = _ENTRIES[entry]
+    L = lib()
+    res = ctypes.POINTER(Result)()
+    check(getattr(L, symbol)(ctypes.byref(args), ctypes.byref(res)))
+    try:
+        yield res.contents
+    finally:
+        getattr(L, free)(res)

@@ -22,24 +22,15 @@ entry), which would drive the persistence pipeline and the bottleneck entry in o
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import numpy as np
 
-from . import _lib
-from .ripser import _arr, _check_common, _data_ptrs, _prep_input, ripser_batch
+from . import _cloud, _lib
+from ._cloud import check_count as _check_count
+from .ripser import _arr, _check_common, ripser_batch
 
 METHODS = ("hausdorff",)
-
-
-def _check_count(name: str, v) -> int:
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-        if not (isinstance(v, (float, np.floating)) and float(v).is_integer()):
-            raise ValueError(f"{name} must be a positive integer, got {v!r}")
-    if v < 1:
-        raise ValueError(f"{name} must be a positive integer, got {v!r}")
-    return int(v)
 
 
 def resample_indices(N: int, B: int, m=None, replace: bool = True, seed: int = 0) -> np.ndarray:
@@ -58,56 +49,15 @@ def resample_indices(N: int, B: int, m=None, replace: bool = True, seed: int = 0
 
 def _check_idx(idx, L: int, N: int) -> np.ndarray:
     """idx as a contiguous int32 (B, m) or (L, B, m) table of indices into 0 .. N-1."""
-    idx = np.asarray(idx)
-    if idx.dtype.kind not in "iu":
-        raise ValueError(f"idx must hold integers, got dtype {idx.dtype}")
-    if idx.ndim not in (2, 3) or idx.size == 0:
-        raise ValueError(f"idx must be a non-empty (B, m) or (L, B, m) table, got shape {idx.shape}")
-    if idx.ndim == 3 and idx.shape[0] != L:
-        raise ValueError(f"a per-layer idx must be (L = {L}, B, m), got shape {idx.shape}")
-    if idx.min() < 0 or idx.max() >= N:
-        raise ValueError(f"idx must hold indices into 0 .. N-1 = {N - 1}, got {int(idx.min())} .. {int(idx.max())}")
-    return np.ascontiguousarray(idx, dtype=np.int32)
+    return _cloud.check_table(idx, None, L, N)[0]
 
 
-class _Input:
-    """One prepared (L, N, D) input of this module's calls, checked before any library call."""
-
-    def __init__(self, X, distance_matrix: bool, device: int):
-        if isinstance(X, (list, tuple)):
-            raise ValueError("resampling needs one (L, N, D) array: input in parts is not supported")
-        self.keep, self.on_dev, device_p, self.is64, self.stream = _prep_input(X, False)
-        self.L, self.N, self.D = (int(s) for s in self.keep.shape)
-        self.is_dist = bool(distance_matrix)
-        if self.is_dist and self.D != self.N:
-            raise ValueError("Distance matrix is not square")
-        if self.is64 and not self.is_dist:
-            raise NotImplementedError("resampling of float64 point clouds is not implemented (sklearn's row-wise and full "
-                                      "float64 distances disagree): pass float32 points or a distance matrix")
-        self.device = int(device_p if self.on_dev else device)
-
-
-def _hausdorff(inp: _Input, idx: np.ndarray):
+def _hausdorff(inp: _cloud.CloudInput, idx: np.ndarray):
     """One tda_resample call: ((L, B) float64 holding f32 values, device ms)."""
     a = _lib.ResampleArgs()
-    a.x = _data_ptrs([inp.keep], inp.on_dev)[0]
-    a.dtype = _lib.TDA_F64 if inp.is64 else _lib.TDA_F32
-    a.x_on_device = 1 if inp.on_dev else 0
-    a.L, a.N, a.D = inp.L, inp.N, inp.D
-    a.is_dist = 1 if inp.is_dist else 0
-    a.device = inp.device
-    a.stream = (inp.stream or None) if inp.on_dev else None
-    a.B, a.m = int(idx.shape[-2]), int(idx.shape[-1])
-    a.idx_per_layer = 1 if idx.ndim == 3 else 0
-    a.idx = idx.ctypes.data
-    L = _lib.lib()
-    res = ctypes.POINTER(_lib.ResampleResult)()
-    _lib.check(L.tda_resample(ctypes.byref(a), ctypes.byref(res)))
-    try:
-        r = res.contents
+    _cloud.fill_table_head(a, inp, idx)
+    with _lib.result("resample", a) as r:
         return _arr(r.hausdorff, inp.L * int(a.B), np.float32).reshape(inp.L, int(a.B)).astype(np.float64), float(r.device_ms)
-    finally:
-        L.tda_resample_free(res)
 
 
 def hausdorff_resamples(X, idx, distance_matrix: bool = False, device: int = 0) -> np.ndarray:
@@ -120,7 +70,7 @@ def hausdorff_resamples(X, idx, distance_matrix: bool = False, device: int = 0) 
     (holding f32 values) ``H[l, b] = max_i min_j dm[l][idx[b][j]][i]`` on the library's own f32
     distance matrix ``dm`` (what ``ripser_batch(X, want_dist=True)`` returns as ``dist``): every
     value is copied from it, so it equals ``dm[l][idx[b]].min(0).max()`` exactly."""
-    inp = _Input(X, distance_matrix, device)
+    inp = _cloud.table_input(X, distance_matrix, device)
     return _hausdorff(inp, _check_idx(idx, inp.L, inp.N))[0]
 
 
@@ -187,7 +137,7 @@ def confidence_bands(X, B: int = 1000, alpha: float = 0.05, method: str = "hausd
     if idx is None:
         B = _check_count("B", B)
         m = None if m is None else _check_count("m", m)
-    inp = _Input(X, distance_matrix, device)
+    inp = _cloud.table_input(X, distance_matrix, device)
     L, N = inp.L, inp.N
     idx = resample_indices(N, B, m, replace, seed) if idx is None else _check_idx(idx, L, N)
     B = int(idx.shape[-2])

@@ -171,8 +171,7 @@ def _matrix(values, S: int, S2: int, block: bool):
 def _library_call(entry: str, points, offsets, pairs, read, **fields):
     """One call of an entry of tda_dgm.h (_lib.DGM_ENTRIES): the common fields and ``fields`` set, the
     return code checked; returns ``read(result struct)`` (owned arrays: _owned) and frees the result."""
-    symbol, free, Args, Result = _lib.DGM_ENTRIES[entry]
-    a = Args()
+    a = _lib.DGM_ENTRIES[entry][2]()
     a.points = points.ctypes.data if len(points) else None
     a.offsets = offsets.ctypes.data
     a.S = len(offsets) - 1
@@ -180,13 +179,8 @@ def _library_call(entry: str, points, offsets, pairs, read, **fields):
         a.pairs, a.P = pairs.ctypes.data, len(pairs)
     for name, value in fields.items():
         setattr(a, name, value)
-    L = _lib.lib()
-    res = ctypes.POINTER(Result)()
-    _lib.check(getattr(L, symbol)(ctypes.byref(a), ctypes.byref(res)))
-    try:
-        return read(res.contents)
-    finally:
-        getattr(L, free)(res)
+    with _lib.result(entry, a) as r:
+        return read(r)
 
 
 def _owned(p, n: int, dtype=np.float64):

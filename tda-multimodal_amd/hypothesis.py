@@ -18,12 +18,10 @@ diagrams per condition.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
 from . import _lib, diagrams
-from .bootstrap import _check_count
+from ._cloud import check_count as _check_count
 
 METRICS = ("sliced_wasserstein", "bottleneck", "wasserstein", "heat", "fisher")
 
@@ -107,18 +105,12 @@ def permutation_test(D, labels, B: int = 9999, q: float = 1.0, seed: int = 0, pe
     a.w, a.obs, a.lab = W.ctypes.data, obs.ctypes.data, lab.ctypes.data
     a.S, a.B, a.G = S, int(lab.shape[0]), len(groups)
     a.device, a.reserved = int(device), 0
-    L = _lib.lib()
-    res = ctypes.POINTER(_lib.PermResult)()
-    _lib.check(L.tda_permutation_test(ctypes.byref(a), ctypes.byref(res)))
-    try:
-        r = res.contents
+    with _lib.result("perm", a) as r:
         out = PermutationTest()
         out.statistic, out.pvalue, out.count, out.B = float(r.t_obs), float(r.pvalue), int(r.count), int(r.B)
         out.groups, out.device_ms = groups, float(r.device_ms)
         out.null = np.ctypeslib.as_array(r.null, shape=(out.B,)).copy() if return_null else None
         return out
-    finally:
-        L.tda_perm_free(res)
 
 
 def diagram_permutation_test(dgms, labels, metric: str = "wasserstein", dim: int = 1, M: int = 50, sigma: float = 0.4, device: int = 0,

@@ -27,8 +27,8 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
-from .ripser import _is_torch, ripser_batch
+from . import _cloud, _lib
+from .ripser import ripser_batch
 
 
 def compute_effective_dimensionality(activations_batch):
@@ -41,23 +41,21 @@ def compute_effective_dimensionality(activations_batch):
     Limit: min(n, d) <= 1024 (the f64 Gram matrix of the smaller side is
     eigen-solved in one workgroup); a full-sequence call with more than 1024
     tokens at D = 4096 (metrics.py:86) raises NotImplementedError."""
-    x, on_dev, device, stream, dev = _f32_input(activations_batch)
-    if not on_dev and x.ndim == 3 and not np.all(np.isfinite(x)):
-        raise ValueError("Input contains NaN or infinity")
+    inp = _cloud.prepare(activations_batch, _cloud.METRICS, ndim=None)
+    x = inp.keep
+    if x.ndim == 3:  # the order of these checks is the one callers have met since the entry exists (DESIGN.md 6.37)
+        inp.require_finite()
     if x.ndim == 3 and min(int(x.shape[1]), int(x.shape[2])) > 1024:
         raise NotImplementedError("compute_effective_dimensionality: min(n_samples, embed_dim) <= 1024 is supported")
     if x.ndim != 3:
         raise ValueError("activations_batch must be (batch_size, n_samples, embed_dim)")
-    ptr = x.data_ptr() if on_dev else x.ctypes.data
-    B, n, d = (int(v) for v in x.shape)
-    out = np.zeros(B, np.float32)
-    if B:
+    inp.shape = tuple(int(v) for v in x.shape)
+    out = np.zeros(inp.L, np.float32)
+    if inp.L:
         a = _lib.EdArgs()
-        a.x, a.dtype, a.x_on_device = ptr, _lib.TDA_F32, on_dev
-        a.B, a.N, a.D = B, n, d
-        a.device, a.stream = int(device), stream
+        _cloud.fill_head(a, inp, names=("B", "N"))
         _lib.check(_lib.lib().tda_effective_dim(ctypes.byref(a), out.ctypes.data_as(_lib._f32p)))
-    return _like_input(out, dev)
+    return _like_input(out, inp.like)
 
 
 def _check_spectral_shape(what, n, d):
@@ -70,13 +68,13 @@ def _check_spectral_shape(what, n, d):
         raise NotImplementedError(f"{what}: n_samples <= 8192 is supported")
 
 
-def _spectral_call(entry, x, on_dev, device, stream, B, S, D, n_windows, out, alphas=None, eps=0.0):
+def _spectral_call(entry, inp, B, S, D, n_windows, out, alphas=None, eps=0.0):
     a = _lib.SpectralArgs()
-    a.x, a.dtype, a.x_on_device = (x.data_ptr() if on_dev else x.ctypes.data), _lib.TDA_F32, on_dev
-    a.B, a.S, a.D, a.n_windows = B, S, D, n_windows
+    inp.shape = (B, S, D)
+    _cloud.fill_head(a, inp, names=("B", "S"))
+    a.n_windows = n_windows
     if alphas is not None:
         a.n_alpha, a.alphas, a.eps = len(alphas), alphas.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), eps
-    a.device, a.stream = int(device), stream
     _lib.check(getattr(_lib.lib(), entry)(ctypes.byref(a), out.ctypes.data_as(_lib._f32p)))
 
 
@@ -101,19 +99,19 @@ def matrix_entropy_profile(matrix, alphas, eps: float = 1e-10):
         raise ValueError("matrix entropy: every order alpha must be finite and > 0")
     if not eps >= 0.0:
         raise ValueError("matrix entropy: eps must be >= 0")
-    x, on_dev, device, stream, dev = _f32_input(matrix)
+    inp = _cloud.prepare(matrix, _cloud.METRICS, ndim=None)
+    x = inp.keep
     if x.ndim < 2:
         raise ValueError("matrix must be (..., N, D)")
     lead = tuple(int(v) for v in x.shape[:-2])
     n, d = int(x.shape[-2]), int(x.shape[-1])
     _check_spectral_shape("matrix_entropy", n, d)
-    if not on_dev and not np.all(np.isfinite(x)):
-        raise ValueError("Input contains NaN or infinity")
+    inp.require_finite()
     B = int(np.prod(lead, dtype=np.int64))
     out = np.zeros((B, al.size), np.float32)
     if B:
-        _spectral_call("tda_matrix_entropy", x, on_dev, device, stream, B, n, d, 0, out, al, float(eps))
-    return _like_input(out.reshape(lead + (al.size,)), dev)
+        _spectral_call("tda_matrix_entropy", inp, B, n, d, 0, out, al, float(eps))
+    return _like_input(out.reshape(lead + (al.size,)), inp.like)
 
 
 def matrix_entropy(matrix, alpha: float = 1.0, eps: float = 1e-10):
@@ -134,7 +132,8 @@ def compute_fixed_window_ed(activations_batch, n_windows: int):
     n_windows = int(n_windows)
     if n_windows <= 0:
         raise ValueError("n_windows must be positive")
-    x, on_dev, device, stream, dev = _f32_input(activations_batch)
+    inp = _cloud.prepare(activations_batch, _cloud.METRICS, ndim=None)
+    x = inp.keep
     if x.ndim != 3:
         raise ValueError("activations_batch must be (batch_size, seq_len, embed_dim)")
     B, S, D = (int(v) for v in x.shape)
@@ -142,12 +141,14 @@ def compute_fixed_window_ed(activations_batch, n_windows: int):
         raise ValueError("compute_fixed_window_ed: seq_len >= 1 is needed")
     W = min(n_windows, S)  # metrics.py:63-73
     _check_spectral_shape("compute_fixed_window_ed", S // W, D)
-    if not on_dev and not np.all(np.isfinite(x)):
-        raise ValueError("Input contains NaN or infinity")
+    inp.require_finite()
     out = np.zeros((B, W), np.float32)
     if B:
-        _spectral_call("tda_effective_dim_windows", x, on_dev, device, stream, B, S, D, W, out)
-    return _like_input(out, dev)
+        _spectral_call("tda_effective_dim_windows", inp, B, S, D, W, out)
+    return _like_input(out, inp.like)
+
+
+_TWONN_EPS = 1e-10  # compute_intrinsic_dimensionality's default, and what its windowed form passes
 
 
 def compute_fixed_window_id(activations_batch, n_windows: int, discard_fraction: float = 0.1):
@@ -157,39 +158,17 @@ def compute_fixed_window_id(activations_batch, n_windows: int, discard_fraction:
     n_windows) float32, all NaN in the reference's cases: n_windows <= 0,
     seq_len < n_windows, seq_len < 6 or a window of fewer than 6 tokens."""
     n_windows = int(n_windows)
-    is_t = _is_torch(activations_batch)
-    x = activations_batch if is_t else np.asarray(activations_batch, dtype=np.float32)
+    inp = _cloud.prepare(activations_batch, _cloud.METRICS, ndim=None)
+    x = inp.keep
     if x.ndim != 3:
         raise ValueError("activations_batch must be (batch_size, seq_len, embed_dim)")
     B, S, D = (int(v) for v in x.shape)
     ws = S // n_windows if n_windows > 0 else 0
     if n_windows <= 0 or S < n_windows or S < 6 or ws < 6:  # metrics.py:228-245
-        return _like_input(np.full((B, max(n_windows, 0)), np.nan, dtype=np.float32), x.device if is_t else None)
+        return _like_input(np.full((B, max(n_windows, 0)), np.nan, dtype=np.float32), inp.like)
     # no remainder: a view of the input; else the kept tokens, copied contiguous
     windows = x[:, : n_windows * ws, :].reshape(B * n_windows, ws, D)
-    return compute_intrinsic_dimensionality(windows, discard_fraction).reshape(B, n_windows)
-
-
-def _f32_input(x):
-    """The input as contiguous float32 (metrics.py:25) where the library reads
-    it: (x, x_on_device, device ordinal, caller's stream, torch device or None);
-    x is a CUDA tensor when x_on_device, else a numpy array."""
-    stream, on_dev, device, dev = None, 0, 0, None
-    if _is_torch(x):
-        import torch
-
-        dev = x.device
-        x = x.detach().to(torch.float32).contiguous()
-        if x.is_cuda:
-            on_dev = 1
-            device = x.device.index if x.device.index is not None else torch.cuda.current_device()
-            raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-            stream = raw(device) if raw else torch.cuda.current_stream(x.device).cuda_stream
-        else:
-            x = x.numpy()
-    if not on_dev:
-        x = np.ascontiguousarray(np.asarray(x), dtype=np.float32)
-    return x, on_dev, device, stream, dev
+    return _like_input(_twonn(windows, discard_fraction, _TWONN_EPS).reshape(B, n_windows), inp.like)
 
 
 def _like_input(out, dev):
@@ -201,7 +180,7 @@ def _like_input(out, dev):
     return torch.from_numpy(np.ascontiguousarray(out)).to(dev)
 
 
-def compute_intrinsic_dimensionality(data, discard_fraction: float = 0.1, eps: float = 1e-10):
+def compute_intrinsic_dimensionality(data, discard_fraction: float = 0.1, eps: float = _TWONN_EPS):
     """TwoNN intrinsic dimension of each (n_samples, embed_dim) item of
     ``data`` (batch, n_samples, embed_dim).  Returns a torch float32 tensor on
     the input's device for torch input, else a numpy float32 array.
@@ -211,29 +190,17 @@ def compute_intrinsic_dimensionality(data, discard_fraction: float = 0.1, eps: f
     agree within the tolerance stated in tests/test_gpu_parity.py.  No
     persistence is computed (TDA_FLAG_NO_PERSISTENCE).  n_samples <= 8192 (the
     per-item ratio sort runs in LDS); the reference has no such limit."""
-    is_t = _is_torch(data)
-    if is_t:
-        import torch
-
-        dev = data.device
-        x = data.detach()
-        if x.dtype != torch.float32:
-            x = x.to(torch.float32)  # metrics.py:140
-        if not x.is_cuda:
-            x = x.numpy()
-    else:
-        x = np.asarray(data, dtype=np.float32)
-    if x.ndim != 3:
+    inp = _cloud.prepare(data, _cloud.METRICS, ndim=None)  # float32: metrics.py:140
+    if inp.keep.ndim != 3:
         raise ValueError("data must be (batch_size, n_samples, embed_dim)")
+    return _like_input(_twonn(inp.keep, discard_fraction, eps), inp.like)
+
+
+def _twonn(x, discard_fraction, eps) -> np.ndarray:
+    """(batch,) float32 TwoNN estimates of prepared (batch, n, d) float32 input."""
     B, n = int(x.shape[0]), int(x.shape[1])
     if n <= 5 or B == 0:  # metrics.py:136-137
-        out = np.full(B, np.nan, dtype=np.float32)
-    else:
-        # distances + k_twonn only (TDA_FLAG_NO_PERSISTENCE): the reference computes no persistence here
-        res = ripser_batch(x, maxdim=0, twonn=True, discard_fraction=discard_fraction, eps=eps, persistence=False)
-        out = np.array([r.twonn for r in res], dtype=np.float32)
-    if is_t:
-        import torch
-
-        return torch.from_numpy(out).to(dev)
-    return out
+        return np.full(B, np.nan, dtype=np.float32)
+    # distances + k_twonn only (TDA_FLAG_NO_PERSISTENCE): the reference computes no persistence here
+    res = ripser_batch(x, maxdim=0, twonn=True, discard_fraction=discard_fraction, eps=eps, persistence=False)
+    return np.array([r.twonn for r in res], dtype=np.float32)

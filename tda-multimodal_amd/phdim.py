@@ -15,13 +15,11 @@ computed; ``E`` is a float64 sum in step order, for alpha 1 and 2 bit for bit a 
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
-from . import _lib
-from .bootstrap import _check_count, _Input
-from .ripser import _arr, _data_ptrs
+from . import _cloud, _lib
+from ._cloud import check_count as _check_count, check_table as _check_table
+from .ripser import _arr
 
 
 def subsample_indices(N: int, sizes, n_trials: int, seed: int = 0):
@@ -42,31 +40,6 @@ def subsample_indices(N: int, sizes, n_trials: int, seed: int = 0):
     return idx, sz
 
 
-def _check_table(idx, sizes, L: int, N: int):
-    """idx as a contiguous int32 (B, m) or (L, B, m) table and sizes as int32 (B,): 1 <= sizes[b] <= m
-    and the first sizes[b] entries of every row are indices into 0 .. N-1 (the rest is never read)."""
-    idx = np.asarray(idx)
-    if idx.dtype.kind not in "iu":
-        raise ValueError(f"idx must hold integers, got dtype {idx.dtype}")
-    if idx.ndim not in (2, 3) or idx.size == 0:
-        raise ValueError(f"idx must be a non-empty (B, m) or (L, B, m) table, got shape {idx.shape}")
-    if idx.ndim == 3 and idx.shape[0] != L:
-        raise ValueError(f"a per-layer idx must be (L = {L}, B, m), got shape {idx.shape}")
-    B, m = int(idx.shape[-2]), int(idx.shape[-1])
-    sizes = np.full(B, m, dtype=np.int32) if sizes is None else np.asarray(sizes)
-    if sizes.dtype.kind not in "iu" or sizes.shape != (B,):
-        raise ValueError(f"sizes must hold B = {B} integers, got dtype {sizes.dtype}, shape {sizes.shape}")
-    if sizes.min() < 1 or sizes.max() > m:
-        raise ValueError(f"sizes must lie in 1 .. m = {m}, got {int(sizes.min())} .. {int(sizes.max())}")
-    used = idx[..., np.arange(m)[None, :] < sizes[:, None]]
-    if used.min() < 0 or used.max() >= N:
-        raise ValueError(f"idx must hold indices into 0 .. N-1 = {N - 1}, got {int(used.min())} .. {int(used.max())}")
-    unused = np.arange(m)[None, :] >= sizes[:, None]
-    if idx.dtype != np.int32 and unused.any():  # what is never read need not fit int32
-        idx = np.where(unused, 0, idx)
-    return np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(sizes, dtype=np.int32)
-
-
 def _check_alpha(alpha) -> float:
     alpha = float(alpha)
     if not np.isfinite(alpha) or alpha <= 0.0:
@@ -74,32 +47,18 @@ def _check_alpha(alpha) -> float:
     return alpha
 
 
-def _subsample_h0(inp: _Input, idx: np.ndarray, sizes: np.ndarray, alpha: float, want_deaths: bool):
+def _subsample_h0(inp: _cloud.CloudInput, idx: np.ndarray, sizes: np.ndarray, alpha: float, want_deaths: bool):
     """One tda_subsample_h0 call: ((L, B) float64, (L, B, m - 1) float32 or None, device ms)."""
     a = _lib.SubsampleH0Args()
-    a.x = _data_ptrs([inp.keep], inp.on_dev)[0]
-    a.dtype = _lib.TDA_F64 if inp.is64 else _lib.TDA_F32
-    a.x_on_device = 1 if inp.on_dev else 0
-    a.L, a.N, a.D = inp.L, inp.N, inp.D
-    a.is_dist = 1 if inp.is_dist else 0
-    a.device = inp.device
-    a.stream = (inp.stream or None) if inp.on_dev else None
-    a.B, a.m = int(idx.shape[-2]), int(idx.shape[-1])
-    a.idx_per_layer = 1 if idx.ndim == 3 else 0
-    a.idx, a.sizes = idx.ctypes.data, sizes.ctypes.data
+    _cloud.fill_table_head(a, inp, idx)
+    a.sizes = sizes.ctypes.data
     a.alpha = alpha
     a.want_deaths = 1 if want_deaths else 0
-    L = _lib.lib()
-    res = ctypes.POINTER(_lib.SubsampleH0Result)()
-    _lib.check(L.tda_subsample_h0(ctypes.byref(a), ctypes.byref(res)))
-    try:
-        r = res.contents
+    with _lib.result("sh0", a) as r:
         B, m = int(a.B), int(a.m)
         E = _arr(r.E, inp.L * B, np.float64).reshape(inp.L, B).copy()
         d = _arr(r.deaths, inp.L * B * (m - 1), np.float32).reshape(inp.L, B, m - 1) if want_deaths else None
         return E, d, float(r.device_ms)
-    finally:
-        L.tda_subsample_h0_free(res)
 
 
 def h0_subsamples(X, idx, sizes=None, alpha: float = 1.0, deaths: bool = False, distance_matrix: bool = False, device: int = 0):
@@ -118,7 +77,7 @@ def h0_subsamples(X, idx, sizes=None, alpha: float = 1.0, deaths: bool = False, 
     (holding f32 values) of the ``sizes[b] - 1`` deaths in that order; sorted, they are the finite
     H0 deaths of ripser on the subsample."""
     alpha = _check_alpha(alpha)
-    inp = _Input(X, distance_matrix, device)
+    inp = _cloud.table_input(X, distance_matrix, device)
     idx, sizes = _check_table(idx, sizes, inp.L, inp.N)
     E, d, _ = _subsample_h0(inp, idx, sizes, alpha, bool(deaths))
     if not deaths:
@@ -158,7 +117,7 @@ def ph_dimension(X, alpha: float = 1.0, sizes=None, n_trials: int = 8, seed: int
     alpha = _check_alpha(alpha)
     if idx is None:
         n_trials = _check_count("n_trials", n_trials)
-    inp = _Input(X, distance_matrix, device)
+    inp = _cloud.table_input(X, distance_matrix, device)
     if idx is None:
         sizes = default_sizes(inp.N) if sizes is None else np.asarray(sizes).reshape(-1)
         if len(np.unique(sizes)) < 2:

@@ -18,13 +18,15 @@ the landmarks only.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import warnings
 import weakref
 
 import numpy as np
 
-from . import _lib
+from . import _cloud, _lib
+from ._cloud import is_torch as _is_torch
 
 
 class _Batch:
@@ -180,10 +182,6 @@ def _call_batch(args: _lib.RipsArgs, want_dist: bool):
         L.tda_rips_free(res)
 
 
-def _is_torch(x) -> bool:
-    return type(x).__module__.startswith("torch")
-
-
 def _check_common(maxdim, coeff, do_cocycles, n_perm, metric):
     if coeff != 2:
         raise NotImplementedError("only coeff=2 (Z/2) is implemented (the reference never overrides it)")
@@ -217,45 +215,6 @@ def encode_labels(label_sets, n: int) -> np.ndarray:
             raise NotImplementedError("silhouette with more than 32 clusters is not implemented")
         rows.append(codes.astype(np.int32))
     return np.ascontiguousarray(np.stack(rows)) if rows else np.zeros((0, n), np.int32)
-
-
-def _prep_input(X, input_ready: bool):
-    """One input array -> (contiguous array kept alive, on_device, device,
-    is_f64, caller stream handle or 0)."""
-    if _is_torch(X) and X.is_cuda:
-        import torch
-
-        if X.dim() != 3:
-            raise ValueError("X must be (L, N, D)")
-        if X.dtype not in (torch.float32, torch.float64):
-            X = X.to(torch.float64)
-        keep = X.contiguous()
-        device = keep.device.index if keep.device.index is not None else torch.cuda.current_device()
-        stream = 0
-        # input_ready: the caller has synchronised after producing X, so no
-        # device-side ordering on its stream (whose queue a pipeline slot may share)
-        if not input_ready:
-            # torch's current stream on that device (raw handle: no Stream object per call)
-            raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-            stream = raw_stream(device) if raw_stream else torch.cuda.current_stream(keep.device).cuda_stream
-        return keep, True, device, keep.dtype == torch.float64, stream
-    if _is_torch(X):
-        X = X.detach().cpu().numpy()
-    X = np.asarray(X)
-    if X.ndim != 3:
-        raise ValueError("X must be (L, N, D)")
-    if X.dtype not in (np.float32, np.float64):
-        X = X.astype(np.float64)
-    # the NaN / infinity check runs in _data_ptrs, over every part in one C call
-    return np.ascontiguousarray(X), False, None, X.dtype == np.float64, 0
-
-
-def _data_ptrs(keeps: list, on_dev: bool) -> list:
-    """Data pointers of one call's prepared inputs; host inputs must be all
-    finite (ripser.py raises "Input contains NaN or infinity.")."""
-    if on_dev:
-        return [k.data_ptr() for k in keeps]
-    return _lib.hostviews().finite_ptrs(keeps)
 
 
 def _fill_call_args(a, N, maxdim, thresh, distance_matrix, want_dist, stage_times, stage_serial, one_stream, input_ready,
@@ -345,41 +304,20 @@ def ripser_batch(X, maxdim: int = 1, thresh: float = np.inf, distance_matrix: bo
                                        stage_serial=stage_serial, twonn=twonn, want_dist64=want_dist64, slot=slot,
                                        persistence=persistence, one_stream=one_stream, input_ready=input_ready)
     a = _lib.RipsArgs()
-    parts = list(X) if isinstance(X, (list, tuple)) else None
-    if parts is not None:  # ABI 6 x_parts: consecutive sweeps of one dynamically batched call
-        if not 1 <= len(parts) <= _lib.TDA_MAX_PARTS:
+    if isinstance(X, (list, tuple)):  # ABI 6 x_parts: consecutive sweeps of one dynamically batched call
+        if not 1 <= len(X) <= _lib.TDA_MAX_PARTS:
             raise ValueError(f"X as parts needs 1 .. {_lib.TDA_MAX_PARTS} arrays")
-        kept = [_prep_input(x, input_ready) for x in parts]
-        k0 = kept[0]
-        for k in kept[1:]:
-            if k[0].shape != k0[0].shape or k[1:4] != k0[1:4]:
+        parts = [_cloud.prepare(x, _cloud.RIPSER, device, input_ready) for x in X]
+        inp = parts[0]
+        for i in parts[1:]:
+            if i.keep.shape != inp.keep.shape or (i.on_dev, i.device, i.dtype) != (inp.on_dev, inp.device, inp.dtype):
                 raise ValueError("parts must share shape, dtype and device")
-        keep_parts = [k[0] for k in kept]
-        ptrs = (ctypes.c_void_p * len(parts))(*_data_ptrs(keep_parts, k0[1]))
-        a.x_parts = ctypes.cast(ptrs, ctypes.c_void_p)
-        a.n_parts = len(parts)
-        keep = k0[0]
-        on_dev, device_p, dtype_is64, stream = k0[1], k0[2], k0[3], k0[4]
-        a.x_on_device = 1 if on_dev else 0
-        if on_dev:
-            device = device_p
-            a.stream = stream or None
-        Lp = int(keep.shape[0])
-        shape = (Lp * len(parts),) + tuple(keep.shape[1:])
     else:
-        keep, on_dev, device_p, dtype_is64, stream = _prep_input(X, input_ready)
-        a.x = _data_ptrs([keep], on_dev)[0]
-        a.x_on_device = 1 if on_dev else 0
-        if on_dev:
-            device = device_p
-            a.stream = stream or None
-        shape = tuple(keep.shape)
-    L, N = int(shape[0]), int(shape[1])
-    if distance_matrix and shape[2] != N:
+        parts, inp = None, _cloud.prepare(X, _cloud.RIPSER, device, input_ready)
+    _cloud.fill_head(a, inp, parts=parts)  # with the finite check of host input: before the shape's
+    _, N, D = inp.shape
+    if distance_matrix and D != N:
         raise ValueError("Distance matrix is not square")
-    a.dtype = _lib.TDA_F64 if dtype_is64 else _lib.TDA_F32
-    a.L, a.N, a.D = L, N, int(shape[2])
-    a.device = int(device)
     a.slot = int(slot)
     want_dist, lab = _fill_call_args(a, N, maxdim, thresh, distance_matrix, want_dist, stage_times, stage_serial, one_stream,
                                      input_ready, persistence, want_dist64, labels, twonn, discard_fraction, eps)
@@ -403,54 +341,41 @@ class GreedyPerm:
     __slots__ = ("idx_perm", "lambdas", "r_cover", "dperm2all", "device_ms", "select_ms")
 
 
-class _GreedyCall:
-    """One tda_greedy_perm call; holds the library-owned result (and with it the
-    landmark matrices on the device) until close()."""
+@contextlib.contextmanager
+def _greedy_call(X, n_perm, distance_matrix, device, want_dperm2all, input_ready=False):
+    """One tda_greedy_perm call: yields (the prepared input, k, the library-owned result); the
+    result, and with it the landmark matrices on the device, lives until the block ends."""
+    if isinstance(X, (list, tuple)):
+        raise ValueError("n_perm needs one (L, N, D) array: input in parts is not supported with it")
+    if n_perm is None or int(n_perm) != n_perm:
+        raise ValueError("n_perm must be an integer")
+    inp = _cloud.prepare(X, _cloud.RIPSER, device, input_ready)
+    inp.is_dist = bool(distance_matrix)
+    _, N, D = inp.shape
+    if distance_matrix and D != N:
+        raise ValueError("Distance matrix is not square")
+    if not 1 <= n_perm <= N:
+        raise ValueError(f"n_perm must be in [1, N = {N}]")
+    if inp.dtype == _lib.TDA_F64 and not distance_matrix:
+        raise NotImplementedError("n_perm with float64 point clouds is not implemented (sklearn's row-wise and full "
+                                  "float64 distances disagree): pass float32 points or a distance matrix")
+    a = _lib.GreedyArgs()
+    _cloud.fill_head(a, inp)
+    a.n_perm = int(n_perm)
+    a.want_dperm2all = 1 if want_dperm2all else 0
+    with _lib.result("greedy", a) as r:
+        yield inp, int(n_perm), r
 
-    def __init__(self, X, n_perm, distance_matrix, device, want_dperm2all, input_ready=False):
-        if isinstance(X, (list, tuple)):
-            raise ValueError("n_perm needs one (L, N, D) array: input in parts is not supported with it")
-        if n_perm is None or int(n_perm) != n_perm:
-            raise ValueError("n_perm must be an integer")
-        keep, on_dev, device_p, is64, stream = _prep_input(X, input_ready)
-        L, N = int(keep.shape[0]), int(keep.shape[1])
-        if distance_matrix and keep.shape[2] != N:
-            raise ValueError("Distance matrix is not square")
-        if not 1 <= n_perm <= N:
-            raise ValueError(f"n_perm must be in [1, N = {N}]")
-        if is64 and not distance_matrix:
-            raise NotImplementedError("n_perm with float64 point clouds is not implemented (sklearn's row-wise and full "
-                                      "float64 distances disagree): pass float32 points or a distance matrix")
-        a = _lib.GreedyArgs()
-        a.x = _data_ptrs([keep], on_dev)[0]
-        a.dtype = _lib.TDA_F64 if is64 else _lib.TDA_F32
-        a.x_on_device = 1 if on_dev else 0
-        a.L, a.N, a.D = L, N, int(keep.shape[2])
-        a.is_dist = 1 if distance_matrix else 0
-        a.n_perm = int(n_perm)
-        a.device = int(device_p if on_dev else device)
-        a.stream = (stream or None) if on_dev else None
-        a.want_dperm2all = 1 if want_dperm2all else 0
-        self.lib = _lib.lib()
-        self.res = ctypes.POINTER(_lib.GreedyResult)()
-        self.L, self.N, self.k, self.device = L, N, int(n_perm), a.device
-        _lib.check(self.lib.tda_greedy_perm(ctypes.byref(a), ctypes.byref(self.res)))
 
-    def unpack(self) -> GreedyPerm:
-        r = self.res.contents
-        L, N, k = self.L, self.N, self.k
-        g = GreedyPerm()
-        g.idx_perm = _arr(r.idx_perm, L * k, np.int64).reshape(L, k)
-        g.lambdas = _arr(r.lambdas, L * k, np.float32).reshape(L, k).astype(np.float64)
-        g.r_cover = g.lambdas[:, -1].copy()
-        g.dperm2all = _arr(r.dperm2all, L * k * N, np.float32).reshape(L, k, N) if bool(r.dperm2all) else None
-        g.device_ms, g.select_ms = float(r.device_ms), float(r.select_ms)
-        return g
-
-    def close(self):
-        if self.res:
-            self.lib.tda_greedy_free(self.res)
-            self.res = ctypes.POINTER(_lib.GreedyResult)()
+def _greedy_unpack(inp, k, r) -> GreedyPerm:
+    L, N, _ = inp.shape
+    g = GreedyPerm()
+    g.idx_perm = _arr(r.idx_perm, L * k, np.int64).reshape(L, k)
+    g.lambdas = _arr(r.lambdas, L * k, np.float32).reshape(L, k).astype(np.float64)
+    g.r_cover = g.lambdas[:, -1].copy()
+    g.dperm2all = _arr(r.dperm2all, L * k * N, np.float32).reshape(L, k, N) if bool(r.dperm2all) else None
+    g.device_ms, g.select_ms = float(r.device_ms), float(r.select_ms)
+    return g
 
 
 def greedy_perm_batch(X, n_perm: int, distance_matrix: bool = False, device: int = 0, want_dperm2all: bool = True) -> GreedyPerm:
@@ -463,11 +388,8 @@ def greedy_perm_batch(X, n_perm: int, distance_matrix: bool = False, device: int
     furthest from the landmarks so far (the lowest index among equal maxima,
     as numpy's argmax).  Returns a :class:`GreedyPerm`; every value in it is
     copied from the distance matrix, so it equals the host loop exactly."""
-    c = _GreedyCall(X, n_perm, distance_matrix, device, want_dperm2all)
-    try:
-        return c.unpack()
-    finally:
-        c.close()
+    with _greedy_call(X, n_perm, distance_matrix, device, want_dperm2all) as (inp, k, r):
+        return _greedy_unpack(inp, k, r)
 
 
 def greedy_perm(X, n_perm: int, distance_matrix: bool = False):
@@ -491,33 +413,15 @@ def _ripser_batch_landmarks(X, n_perm, maxdim, thresh, distance_matrix, device, 
                          "reference's scores of the cloud")
     if want_dist64:
         raise NotImplementedError("want_dist64 needs float64 point clouds, which n_perm does not take")
-    c = _GreedyCall(X, n_perm, distance_matrix, device, False, input_ready)
-    try:
-        g = c.unpack()
+    with _greedy_call(X, n_perm, distance_matrix, device, False, input_ready) as (inp, k, r):
+        g = _greedy_unpack(inp, k, r)
+        L = inp.shape[0]
         a = _lib.RipsArgs()
-        a.x = c.res.contents.sub_dev
-        a.dtype = _lib.TDA_F32
-        a.x_on_device = 1
-        a.L, a.N, a.D = c.L, c.k, c.k
-        a.is_dist = 1
-        a.maxdim = int(maxdim)
-        a.thresh = float(thresh) if np.isfinite(thresh) else float("inf")
-        a.modulus = 2
-        a.device = c.device
+        _cloud.fill_head(a, _cloud.on_device(r.sub_dev, (L, k, k), inp.device))
         a.slot = int(slot)
-        a.want_dist = 1 if want_dist else 0
-        a.flags = _lib.TDA_FLAG_INPUT_READY
-        if stage_times:
-            a.flags |= _lib.TDA_FLAG_STAGE_TIMES | (_lib.TDA_FLAG_STAGE_SERIAL if stage_serial else 0)
-        if one_stream:
-            a.flags |= _lib.TDA_FLAG_ONE_STREAM
-        if not persistence:
-            if maxdim != 0:
-                raise ValueError("persistence=False needs maxdim=0")
-            a.flags |= _lib.TDA_FLAG_NO_PERSISTENCE
+        want_dist, _ = _fill_call_args(a, k, maxdim, thresh, True, want_dist, stage_times, stage_serial, one_stream, True,
+                                       persistence, False, None, False, 0.0, 0.0)
         out, info = _call_batch(a, want_dist)
-    finally:
-        c.close()
     b = out[0][0]
     b.ip, b.rc = g.idx_perm, g.r_cover
     info = dict(info, greedy_device_ms=g.device_ms, greedy_select_ms=g.select_ms)
@@ -845,9 +749,9 @@ class SweepPipeline:
             self._reap()
         L = _lib.lib()
         try:
-            keep, on_dev, device, is64, _ = _prep_input(X, True)
-            Ls, N, D = keep.shape
-            t = self._template(args, kw, device if on_dev else self.device, N)
+            inp = _cloud.prepare(X, _cloud.RIPSER, self.device, True)
+            Ls, N, D = inp.shape
+            t = self._template(args, kw, inp.device, N)
             if t.is_dist and D != N:
                 raise ValueError("Distance matrix is not square")
             if self._np is None:
@@ -857,12 +761,12 @@ class SweepPipeline:
                         _lib.check(L.tda_pipe_create(self.depth, self.coalesce, ctypes.byref(h)))
                         self._np = h
             ticket = ctypes.c_uint64()
-            _lib.check(L.tda_pipe_submit(self._np, t.ref, t.id, keep.data_ptr() if on_dev else keep.ctypes.data, Ls, N, D,
-                                         _lib.TDA_F64 if is64 else _lib.TDA_F32, 1 if on_dev else 0, ctypes.byref(ticket)))
+            _lib.check(L.tda_pipe_submit(self._np, t.ref, t.id, inp.ptr if inp.on_dev else inp.keep.ctypes.data, Ls, N, D,
+                                         inp.dtype, 1 if inp.on_dev else 0, ctypes.byref(ticket)))
         except Exception as e:
             return _NativeFuture(self, None, None, e)
         # from here on a worker may read the array: the pipeline holds it until the call has run
-        self._keeps[ticket.value] = (keep, t)
+        self._keeps[ticket.value] = (inp.keep, t)
         f = _NativeFuture(self, ticket.value, t)
         self._tickets[f._ticket] = weakref.ref(f)
         return f

@@ -21,18 +21,11 @@ from functools import lru_cache
 
 import numpy as np
 
-from . import _lib
+from . import _cloud, _lib
 
 _METRICS = {"euclidean": 0, "l2": 0, "cosine": 1}
 # umap.umap_.DISCONNECTION_DISTANCES: transform drops neighbours at or beyond this distance
 _DISCONNECTION = {"cosine": 2.0}
-
-
-def _raw_stream(dev_index: int):
-    import torch
-
-    raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-    return raw(dev_index) if raw else torch.cuda.current_stream(dev_index).cuda_stream
 
 
 @lru_cache(maxsize=64)
@@ -65,42 +58,15 @@ def umap_batch(X, n_neighbors: int = 15, n_components: int = 2, metric: str = "e
         raise NotImplementedError(f"metric {metric!r}: only 'euclidean' and 'cosine' are supported")
     if init not in ("spectral", "random"):
         raise NotImplementedError("init must be 'spectral' or 'random'")
-    on_dev = hasattr(X, "is_cuda") and bool(X.is_cuda)
-    stream = None
-    if on_dev:
-        if X.dim() != 3:
-            raise ValueError("X must be (L, N, D)")
-        Xc = X.contiguous()
-        dtype = {"torch.float32": _lib.TDA_F32, "torch.float64": _lib.TDA_F64}.get(str(Xc.dtype))
-        if dtype is None:
-            raise ValueError("X must be float32 or float64")
-        L, N, D = Xc.shape
-        ptr = Xc.data_ptr()
-        # the tensor's own device, ordered after torch's current stream there
-        if Xc.device.index is not None:
-            device = Xc.device.index
-        stream = _raw_stream(device)
-    else:
-        Xc = np.asarray(X)
-        if Xc.ndim != 3:
-            raise ValueError("X must be (L, N, D)")
-        if Xc.dtype != np.float64:
-            Xc = Xc.astype(np.float32)
-        Xc = np.ascontiguousarray(Xc)
-        if not np.all(np.isfinite(Xc)):
-            raise ValueError("Input contains NaN or infinity")
-        dtype = _lib.TDA_F64 if Xc.dtype == np.float64 else _lib.TDA_F32
-        L, N, D = Xc.shape
-        ptr = Xc.ctypes.data
+    inp = _cloud.prepare(X, _cloud.UMAP, device)
+    inp.require_finite()
+    L, N = inp.L, inp.N
     if a is None or b is None:
         a, b = find_ab_params(spread, min_dist)
     out = np.empty((L, N, n_components), np.float32)
     graph = np.empty((L, N, N), np.float32) if return_graph else None
     args = _lib.UmapArgs()
-    args.x = ptr
-    args.dtype = dtype
-    args.x_on_device = 1 if on_dev else 0
-    args.L, args.N, args.D = L, N, D
+    _cloud.fill_head(args, inp)
     args.metric = _METRICS[metric]
     args.n_neighbors = int(n_neighbors)
     args.n_components = int(n_components)
@@ -111,10 +77,8 @@ def umap_batch(X, n_neighbors: int = 15, n_components: int = 2, metric: str = "e
     args.learning_rate = float(learning_rate)
     args.repulsion_strength = float(repulsion_strength)
     args.seed = int(random_state if random_state is not None else np.random.randint(0, 2**31 - 1)) & (2**64 - 1)
-    args.device = int(device)
     args.out = out.ctypes.data
     args.graph_out = graph.ctypes.data if graph is not None else None
-    args.stream = stream
     _lib.check(_lib.lib().tda_umap_batch(ctypes.byref(args)))
     return (out, graph) if return_graph else out
 
