@@ -434,6 +434,94 @@ int tda_subsample_h0(const tda_subsample_h0_args *args, tda_subsample_h0_result 
 void tda_subsample_h0_free(tda_subsample_h0_result *r);
 
 /*
+ * Geodesic distances over the neighbourhood graph of L layers on the GPU:
+ * Isomap's metric, the input of persistent homology in Naitzat, Zhitnikov and
+ * Lim 2020 ("Topology of deep neural networks").  The result is a distance
+ * matrix for the entries that take one (tda_rips_batch, tda_subsample_h0,
+ * tda_resample, tda_greedy_perm with is_dist).
+ * Per layer, dm is the matrix of tda_resample: the library's own f32
+ * distances, symmetric with a zero diagonal.
+ * The graph.  Exactly one of n_neighbors = k >= 1 and radius >= 0 is given
+ * (n_neighbors = 0 and radius < 0 mean "not given"; radius may be +inf).
+ *   kNN: with ord(w) the unsigned integer ordered as the floats are (-0.0 as
+ *     +0.0; tda_subsample_h0's) and key(i, j) = ord(dm[i][j]) << 32 | j, the
+ *     neighbours of row i are the min(k, N - 1) columns j != i of smallest
+ *     key: the lowest index wins ties.  {i, j} is an edge if j is a neighbour
+ *     of i OR i is a neighbour of j.
+ *   radius: {i, j}, i != j, is an edge iff (double)dm[i][j] <= radius.
+ * W[i][j] = dm[i][j] on an edge, +inf otherwise, W[i][i] = 0.
+ * The closure.  G is the min-plus closure of W in f32: every G[i][j] is the
+ * result of a tree of rounded f32 additions over the edge weights of one walk
+ * from i to j in the graph (W[i][j] itself, or 0 for i == j, when the tree is
+ * a leaf), and no walk gives a smaller result under the same schedule.  For
+ * every schedule: G[i][i] = 0; G[i][j] and G[j][i] are the same bits;
+ * G[i][j] <= W[i][j]; G[i][j] = +inf exactly when i and j lie in different
+ * components (while every walk sum stays finite in f32: weights up to
+ * FLT_MAX / N); a layer's bits do not depend on L, on the chunk of layers it
+ * is served in, or on the other layers of the call.
+ * With G* the exact shortest length, u = 2^-24 and c the height of the
+ * deepest tree the schedule can build,
+ *     |G[i][j] - G*[i][j]| <= ((1 + u)^c - 1) * G*[i][j]
+ * (rounded addition and min are monotone: by induction over the schedule's
+ * steps the computed value lies between (1 - u)^h and (1 + u)^h times the
+ * exact value of that step, h the height so far).  Two schedules:
+ *   N <= 128: the ascending-k loop G[i][j] = min(G[i][j], G[i][k] + G[k][j]),
+ *     k = 0 .. N-1.  A step adds at most 1 to a height and the steps k == i
+ *     and k == j change nothing: c = max(N - 2, 0) <= N - 1.
+ *   N > 128: tiles of B = 64, T = ceil(N / 64) rounds.  Round t closes the
+ *     diagonal tile with the ascending-k loop (+B), then forms the tiles of
+ *     its row as one min-plus product with the closed tile (+1), then every
+ *     other tile as one product of two of those (+1): c = (B + 2) * T.
+ * Where every walk sum is exact in f32 (small integer weights) G == G* bit
+ * for bit under either schedule.
+ * Outputs: dist[l] = G (or W with graph_only, the closure skipped);
+ * n_components[l] = the number of rows i with no finite G[i][j], j < i
+ * (-1 with graph_only); n_edges[l] = the undirected edges of the graph.
+ * Non-finite or negative distances: host matrices that hold them are refused;
+ * device input is not checked, the result for it is unspecified, and every
+ * kernel still terminates and stays in bounds (no loop's trip count and no
+ * address depends on a value of dm).
+ * The call is of the resampling family: it runs on tda_resample's stream and
+ * workspace (it adds neither to the process), captures no graph, and
+ * synchronises before it returns.  The workspace holds the distance stage of
+ * Lc layers at a time (as tda_resample; the rows' thresholds count in); the
+ * graph and the closure are formed in place on dm and read back chunk by
+ * chunk.  N <= 8192 and L * N * N <= 2^28 (the result takes at most 1 GiB).
+ * Checked on the host before any device work, in this order: a NULL pointer,
+ * L, N, D < 1 or a bad dtype, n_neighbors < 0, a NaN radius, both or neither
+ * of n_neighbors and radius: TDA_E_INVALID.  N > 8192, L * N * N > 2^28,
+ * float64 POINT clouds: TDA_E_UNSUPPORTED.  Last, a host distance matrix with
+ * an entry that is not finite and >= 0: TDA_E_INVALID.
+ * Added to ABI 8 (new symbols only; no existing struct changed).
+ */
+#define TDA_GEO_MAX_OUT (1ll << 28)
+
+typedef struct tda_geodesic_args {
+    const void *x;          /* (L, N, D) points or (L, N, N) distances, host or device */
+    int32_t dtype;          /* TDA_F32 | TDA_F64 (TDA_F64: distance matrices only)  */
+    int32_t x_on_device;    /* 1: x is a device pointer on `device`                 */
+    int64_t L, N, D;        /* D ignored when is_dist                               */
+    int32_t is_dist;        /* 1: x holds (L, N, N) distance matrices (upper used)  */
+    int32_t device;         /* HIP device ordinal                                   */
+    void *stream;           /* device input is read after it; NULL = null stream    */
+    int32_t n_neighbors;    /* k >= 1: the kNN graph; 0: not given                  */
+    int32_t graph_only;     /* 1: return W, skip the closure                        */
+    double radius;          /* >= 0 (+inf allowed): the radius graph; < 0: not given */
+} tda_geodesic_args;
+
+typedef struct tda_geodesic_result {
+    int64_t L, N;
+    const float *dist;           /* host [L][N][N]: G, or W with graph_only          */
+    const int32_t *n_components; /* host [L]; -1 with graph_only                     */
+    const int64_t *n_edges;      /* host [L]                                         */
+    int32_t device;
+    double device_ms;            /* device time of the call (HIP events)             */
+} tda_geodesic_result;
+
+int tda_geodesic(const tda_geodesic_args *args, tda_geodesic_result **out);
+void tda_geodesic_free(tda_geodesic_result *r);
+
+/*
  * The permutation test between groups of diagrams (Robinson and Turner 2017,
  * "Hypothesis testing for topological data analysis") on the GPU.  Inputs, all
  * on the host: w, an (S, S) float64 matrix of the q-th powers of the pairwise

@@ -7,12 +7,13 @@ include/tda_rips.h; no CPU fallback.
 """
 import sys as _sys
 
-from . import bootstrap, diagrams, distributed, hypothesis, metrics, phdim, synthetic, umap  # noqa: F401
+from . import bootstrap, diagrams, distributed, geodesic, hypothesis, metrics, phdim, synthetic, umap  # noqa: F401
 from .bootstrap import ConfidenceBands, confidence_bands, hausdorff_resamples, resample_indices  # noqa: F401
 from .diagrams import (betti_curve, betti_curves, bottleneck, bottleneck_matrix, entropy_curve, entropy_curves, fisher,  # noqa: F401
                        fisher_kernel_matrix, fisher_matrix, heat, heat_kernel_matrix, heat_matrix, lifespan_curve, lifespan_curves, persistence_curves, persistence_image, persistence_images,
                        persistence_landscape, persistence_landscapes, persistence_silhouette, persistence_silhouettes, sliced_wasserstein,
                        sliced_wasserstein_kernel, sliced_wasserstein_matrix, wasserstein, wasserstein_matrix)
+from .geodesic import GeodesicDistances, geodesic_distances  # noqa: F401
 from .phdim import PHDimension, h0_subsamples, ph_dimension, subsample_indices  # noqa: F401
 from .hypothesis import PermutationTest, diagram_permutation_test, label_permutations, permutation_test  # noqa: F401
 from .metrics import (compute_effective_dimensionality, compute_fixed_window_ed, compute_fixed_window_id,  # noqa: F401
@@ -68,6 +69,8 @@ __all__ = [
     "PHDimension",
     "h0_subsamples",
     "subsample_indices",
+    "geodesic_distances",
+    "GeodesicDistances",
     "permutation_test",
     "diagram_permutation_test",
     "label_permutations",

@@ -254,6 +254,35 @@ class SubsampleH0Result(ctypes.Structure):  # include/tda_rips.h tda_subsample_h
     ]
 
 
+class GeodesicArgs(ctypes.Structure):  # include/tda_rips.h tda_geodesic_args
+    _fields_ = [
+        ("x", ctypes.c_void_p),
+        ("dtype", ctypes.c_int32),
+        ("x_on_device", ctypes.c_int32),
+        ("L", ctypes.c_int64),
+        ("N", ctypes.c_int64),
+        ("D", ctypes.c_int64),
+        ("is_dist", ctypes.c_int32),
+        ("device", ctypes.c_int32),
+        ("stream", ctypes.c_void_p),
+        ("n_neighbors", ctypes.c_int32),  # k >= 1, or 0: not given
+        ("graph_only", ctypes.c_int32),
+        ("radius", ctypes.c_double),  # >= 0, or < 0: not given
+    ]
+
+
+class GeodesicResult(ctypes.Structure):  # include/tda_rips.h tda_geodesic_result
+    _fields_ = [
+        ("L", ctypes.c_int64),
+        ("N", ctypes.c_int64),
+        ("dist", _f32p),
+        ("n_components", ctypes.POINTER(ctypes.c_int32)),
+        ("n_edges", _i64p),
+        ("device", ctypes.c_int32),
+        ("device_ms", ctypes.c_double),
+    ]
+
+
 class PermArgs(ctypes.Structure):  # include/tda_rips.h tda_perm_args
     _fields_ = [
         ("w", ctypes.c_void_p),  # host float64 (S, S)
@@ -291,6 +320,10 @@ TDA_RESAMPLE_MAX_OUT = 1 << 27  # resamples (L * B) of one call
 TDA_SH0_MAX_OUT = 1 << 27  # subsamples (L * B), and deaths (L * B * (m - 1)), of one tda_subsample_h0 call
 TDA_SH0_LDS_N = 128  # csrc/sh0_kernels.h kSh0LdsN: the largest N whose matrix k_subsample_h0 stages in LDS
 TDA_SH0_LDS_M = 128  # csrc/sh0_kernels.h kSh0LdsM: the largest row length of that path
+TDA_GEO_MAX_N = 8192  # N of a tda_geodesic call
+TDA_GEO_MAX_OUT = 1 << 28  # values (L * N * N) of one tda_geodesic call
+TDA_GEO_LDS_N = 128  # csrc/geo_kernels.h kGeoLdsN: the largest N whose matrix k_geo_resident closes in LDS
+TDA_GEO_TILE = 64  # csrc/geo_kernels.h kGeoTile: the side of a tile of the blocked closure
 
 
 class SwArgs(ctypes.Structure):  # include/tda_dgm.h tda_sw_args
@@ -541,7 +574,7 @@ class UmapTransformArgs(ctypes.Structure):  # include/tda_umap.h
 # every symbol declared in include/tda_rips.h and include/tda_umap.h
 EXPORTS = ("tda_rips_batch", "tda_rips_dm", "tda_rips_free", "tda_last_error", "tda_version", "tda_device_ok",
            "tda_effective_dim", "tda_effective_dim_windows", "tda_matrix_entropy", "tda_greedy_perm", "tda_greedy_free",
-           "tda_resample", "tda_resample_free", "tda_permutation_test", "tda_perm_free", "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan", "tda_debug_attempts",
+           "tda_resample", "tda_resample_free", "tda_geodesic", "tda_geodesic_free", "tda_permutation_test", "tda_perm_free", "tda_umap_batch", "tda_umap_transform", "tda_debug_dist_plan", "tda_debug_attempts",
            "tda_pipe_create", "tda_pipe_submit", "tda_pipe_flush", "tda_pipe_wait", "tda_pipe_release", "tda_pipe_destroy")
 # the entries of include/tda_dgm.h, all of one shape, int entry(const args*, result**) and void free(result*):
 # name -> (entry symbol, free symbol, args struct, result struct)
@@ -571,6 +604,7 @@ SIDE_ENTRIES = {
     "greedy": ("tda_greedy_perm", "tda_greedy_free", GreedyArgs, GreedyResult),
     "resample": ("tda_resample", "tda_resample_free", ResampleArgs, ResampleResult),
     "sh0": SUBSAMPLE_H0_EXPORTS + (SubsampleH0Args, SubsampleH0Result),
+    "geo": ("tda_geodesic", "tda_geodesic_free", GeodesicArgs, GeodesicResult),
     "perm": ("tda_permutation_test", "tda_perm_free", PermArgs, PermResult),
 }
 _ENTRIES = {**DGM_ENTRIES, **SIDE_ENTRIES}

@@ -1239,6 +1239,8 @@ void tda_pipe_destroy(tda_pipe* pipe) { delete pipe; }
 #include "resample_host.h"
 // H0 persistence of subsamples for the persistent-homology dimension (include/tda_rips.h tda_subsample_h0)
 #include "sh0_host.h"
+// geodesic distances over the neighbourhood graph (include/tda_rips.h tda_geodesic)
+#include "geo_host.h"
 // the permutation test between groups of diagrams (include/tda_rips.h tda_permutation_test)
 #include "perm_host.h"
 // sliced Wasserstein distances between persistence diagrams (include/tda_dgm.h)
